@@ -10,7 +10,15 @@ AdamW, all on the libgaext HIP kernels.  Prints ONE JSON line (rank 0).
 children, before this process touches a GPU) and prints rank 0's line; under `python -m torch.distributed.run` it is one
 of the ranks (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment).
 
-Extra objects:
+A plain run sets up, warms up, times --steps steps and prints the line (`ms_per_step` = milliseconds per timed step).
+The optimizer runs at learning rate 0 by default (--lr): every step does the whole update pass, but the parameters stay at
+their seeded values, so every step computes the same thing from the same inputs.  With lr > 0 the rounding differences of
+the kernels' float atomic reductions feed the next step; AdamW's first updates (lr * sign of the gradient) turn them into
+percent-level differences between two runs within 25 steps.
+`--dump-outputs DIR` then writes what the last timed step produced (see dump_outputs) as DIR/<name>.npy; the inputs are
+seeded, so two builds can be compared output for output.
+
+Extra objects, only with `--full` (`--kernel-table PATH` implies it):
   roofline     -- the dominant kernel family of the step (by summed device time), timed per launch with HIP events on the
                   launch stream in a separate instrumented step; achieved = its algorithmic FLOPs (2*M*N*K per GEMM launch)
                   / its device time; `step_frac` = whole-step img/s * GFLOP/img / peak.  `measured_peaks` = this box's own
@@ -60,19 +68,28 @@ def parse():
     ap.add_argument('--batch', type=int, default=256, help='per-GPU batch (the headline config is 256)')
     ap.add_argument('--model', default=MODEL)
     ap.add_argument('--opt', default='adamw')
+    ap.add_argument('--lr', type=float, default=0.0,
+                    help='optimizer learning rate (default 0: the full update pass runs, the parameters keep their seeded values)')
     ap.add_argument('--math', default='bf16', choices=['bf16', 'fp32'])
+    ap.add_argument('--full', action='store_true', help='also the instrumented per-kernel step (roofline, kernel families), '
+                    'the measured peaks and the CPU baseline; the --no-* switches below drop single parts of it')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help="after the timed steps, write the last step's outputs (loss, logits, optimizer moment, parameters, buffers) "
+                         'as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-kernel-times', action='store_true')
     ap.add_argument('--no-measured-peaks', action='store_true')
     ap.add_argument('--no-ddp-bb', action='store_true', help='no per-forward BatchNorm buffer broadcast (GA/train.py:283)')
-    ap.add_argument('--kernel-table', default='', help='write the per-kernel-family table (json) here')
+    ap.add_argument('--kernel-table', default='', help='write the per-kernel-family table (json) here (implies --full)')
     ap.add_argument('--overlap-optimizer', action='store_true', help='optimizer update behind each gradient bucket instead of '
                     'after the whole backward (A/B: slower on one GPU)')
     ap.add_argument('--comm', default='torch', choices=['torch', 'native', 'native-bf16'],
                     help="gradient exchange for N > 1: torch.distributed's nccl (= RCCL) backend, or the library's own RCCL entry points "
                          '(ga_allreduce_bucket; native-bf16: bf16 wire)')
     ap.add_argument('--force-buckets', action='store_true', help='N = 1: still run the segmented backward + bucket reductions')
-    return ap.parse_args()
+    a = ap.parse_args()
+    a.full = a.full or bool(a.kernel_table)
+    return a
 
 
 def kernel_family(label):
@@ -226,6 +243,33 @@ def cpu_baseline(model_name, budget_s=10.0):
                        f'step {best:.3f}s, {mod} on the host CPU')
 
 
+def _sample(t, n, seed):
+    """t whole when it has at most n elements, else n of its elements (flattened) at fixed seeded positions, in order"""
+    if t.numel() <= n:
+        return t
+    idx = torch.randint(0, t.numel(), (n,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return t.reshape(-1)[idx.to(t.device)]
+
+
+def dump_outputs(path, loss, logits, flat, moment):
+    """what a caller of the train step holds after the last timed step, as float32 DIR/<name>.npy (at most 64 MB in all):
+    the loss and the fp32 logits of that step's forward (every head), the optimizer's first moment (AdamW / LAMB `m`, SGD's
+    momentum buffer: an average of every step's reduced gradients, so backward and the gradient exchange), the flat
+    parameters and float buffers as the optimizer and forward left them; arrays over 4 Mi elements (1 Mi for the buffers) as
+    fixed seeded samples.  At the default --lr 0 the parameters keep their seeded values, so every step starts from the same
+    state and two runs differ by the rounding of one step's float atomic reductions."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = dict(loss=loss.reshape(-1), logits=_sample(logits, 1 << 22, 1), moment=_sample(moment, 1 << 22, 4),
+                  params=_sample(flat['params'], 1 << 22, 2))
+    if flat['buffers'].numel():
+        arrays['buffers'] = _sample(flat['buffers'], 1 << 20, 3)
+    out = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    assert sum(v.nbytes for v in out.values()) <= 64 << 20
+    for k, v in out.items():
+        np.save(os.path.join(path, k + '.npy'), v)
+
+
 def spawn_workers(a):
     """`bench.py --gpus N` outside a launcher: N fresh one-GPU children (this process makes no GPU call); rank 0's JSON line
     is passed through.  GA_DIST_BACKEND=gloo + fewer devices than ranks = rehearsal (ranks share a device)."""
@@ -272,7 +316,7 @@ def main():
     if world > 1:  # DDP-style start: rank 0's parameters and buffers everywhere (GA/train.py:514)
         dist.broadcast(model.flat_state()['params'], 0)
         dist.broadcast(model.flat_state()['buffers'], 0)
-    opt = A.create_optimizer_v2(model, opt=a.opt, lr=1e-3, weight_decay=0.05, momentum=0.9)
+    opt = A.create_optimizer_v2(model, opt=a.opt, lr=a.lr, weight_decay=0.05, momentum=0.9)
     comm = None
     if a.comm != 'torch' and (world > 1 or a.force_buckets):
         comm = A.NativeComm(wire='bf16' if a.comm == 'native-bf16' else 'fp32')
@@ -303,19 +347,22 @@ def main():
     ms_per_step = elapsed / a.steps * 1e3
     value = a.batch * world * a.steps / elapsed
     loss_val = float(loss)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, loss, step.eng.logits, model.flat_state(), opt.m if hasattr(opt, 'm') else opt.buf)
     gflop = GFLOP_PER_IMG.get(a.model)
     label = LABEL.get(a.model, a.model)
 
     out = dict(metric=f'images/sec (whole node) {label} 3x{img}x{img} {a.math} training step', value=round(value, 1),
                unit='images/sec', n_gpus=world, steps=a.steps, warmup=a.warmup, ms_per_step=round(ms_per_step, 3),
                higher_is_better=True, scaling='weak', vs_baseline=None, dtype=a.math, data='synthetic',
-               config=dict(workload=f'{a.model} train step (fwd + GA loss lam=-0.8 + bwd + all-reduce + {a.opt}), '
+               config=dict(workload=f'{a.model} train step (fwd + GA loss lam=-0.8 + bwd + all-reduce + {a.opt} lr={a.lr:g}), '
                                     f'batch {a.batch}/GPU, drop_path 0.2, synthetic 3x{img}x{img}',
                            global_batch=a.batch * world, parallelism=f'dp{world}', dist_backend=backend, grad_exchange=a.comm,
                            allreduce_buckets=len(step.buckets), gflop_per_img=gflop),
                loss=round(loss_val, 4), library=A._lib.config_string())
 
-    if rank == 0 and not a.no_kernel_times:
+    # --full only: the instrumented step below runs the plans (and the optimizer) once more
+    if rank == 0 and a.full and not a.no_kernel_times:
         eng = step.eng
         fams, calls = {}, []
         eng.set_input(x)
@@ -365,7 +412,7 @@ def main():
             with open(a.kernel_table, 'w') as fh:
                 json.dump(dict(total_ms=total_ms, families=table,
                                top_calls=sorted(calls, key=lambda c: -c["ms"])), fh, indent=1)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(a.model)
     if rank == 0:
         print(json.dumps(out), flush=True)
