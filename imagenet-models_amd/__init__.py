@@ -22,6 +22,8 @@ from . import map_pit  # noqa: E402,F401  (registers map_pit_s)
 from . import convnext  # noqa: E402,F401  (registers the plain convnext_tiny / convnext_small of map_convnext.py)
 from .convnext import ConvNeXt  # noqa: E402,F401
 from .map_pit import MAP_PiT  # noqa: E402,F401
+from . import mobilenet  # noqa: E402,F401  (registers the extra names mobilenet_v1 / map_mobilenet_v1)
+from .mobilenet import MobileNetV1  # noqa: E402,F401
 from .loss import ga_loss, heads_topk, accuracy_from_topk, map_loss, heads_mean_topk  # noqa: E402,F401
 from .optim import create_optimizer_v2, FusedSGD, FusedAdamW, FusedLamb, CosineLRScheduler  # noqa: E402,F401
 from .mixup import Mixup  # noqa: E402,F401

@@ -864,12 +864,13 @@ class GAEngine:
     # n = gi*gc + ci  <-  fc1 output channel ci*mg + gi; with Nv = gc / mg rows per "virtual group" the fc1 input group is
     # constant inside one (= v % mg), so fc1 is a batched GEMM over mg*mg virtual groups and fc2 one over mg groups.
     # ------------------------------------------------------------------------------------------
-    def _gmlp_fwd(self, pre, t, rows, C, mg, out, R, rowscale, rps, gamma_name=None, act='gelu', drop_mask=None):
+    def _gmlp_fwd(self, pre, t, rows, C, mg, out, R, rowscale, rps, gamma_name=None, act='gelu', drop_mask=None, ratio=4):
         """out = R + rowscale * gamma * fc2(shuffle(drop(act(fc1(t)))));  pre = '<block>.mlp.';  act 'gelu' (GA) or 'relu'
-        (MAP, map.py:467) with an optional dropout mask [rows, 4C] on the hidden layer (in the SHUFFLED channel order)"""
+        (MAP, map.py:467) with an optional dropout mask [rows, ratio * C] on the hidden layer (in the SHUFFLED channel order);
+        ratio: the hidden width over C (mlp_ratio; with mg = 1 the channel shuffle is the identity)"""
         F, dt, P, T = self.fwd, self.dt, self.P, self.training
         gamma = self._pw(gamma_name) if gamma_name else None
-        Hd = 4 * C
+        Hd = int(ratio * C)
         gc_ = Hd // mg
         Nv = gc_ // mg          # rows per virtual group (fc1 input group is constant inside one)
         cin = C // mg
@@ -881,6 +882,7 @@ class GAEngine:
             # columns cin -> cin_p; fc2 rows and columns in groups of cin -> cin_p; ga_pad_groups_f32) and group-padded copies of
             # its input / residual; padded hidden and output channels are exact zeros (zero weights, zero biases), the real part
             # of the output is compacted back and the real part of every padded gradient copied back after the backward pass
+            assert Hd == 4 * C, 'the padded odd-width layout is laid out for mlp_ratio 4'
             cin_p = pad8(cin)
             Cp = mg * cin_p
             self._pad_groups(pre + 'fc1.weight', Hd, cin, 4 * cin, 4 * cin_p, cin, cin_p)

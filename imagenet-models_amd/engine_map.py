@@ -25,6 +25,7 @@ from .ops import Plan
 
 
 class MAPEngine(GAEngine):
+    HP = 'head.'        # parameter-name prefix of the MAPHead (MobileNetV1 holds it as `fc.`)
     NAMES = dict(stem_conv='downsample_layers.0.0.', stem_ln='downsample_layers.0.1.', ds_ln='downsample_layers.{i}.0.',
                  ds_conv='downsample_layers.{i}.1.', block='stages.{i}.{j}.', dw='dwconv.', fc1='pwconv1.', fc2='pwconv2.')
 
@@ -65,15 +66,24 @@ class MAPEngine(GAEngine):
 
     def _multi_scale_conv_fwd(self, cat, M4, ctot):
         """MultiScale.concat_conv (map.py:322-333): conv1x1 -> BN -> GELU on the concat of the resized maps"""
+        return self._conv1x1_bn_act_fwd(cat, M4, ctot, self.HP + 'mmcap.multi_scale.concat_conv.', 'gelu')
+
+    def _conv1x1_bn_act_fwd(self, cat, M4, ctot, mp, act):
+        """ConvNormAct(kernel_size=1) of the MAP head (map.py:280-287) with parameter prefix `mp`: conv1x1 -> BN -> act, act 'gelu'
+        (MultiScale.concat_conv with non_linearity=nn.GELU) or 'relu' (MAP.channel_convertor, map.py:356-364: the default ReLU)"""
         F, dt, T, L = self.fwd, self.dt, self.training, self.cfg['last_dim']
-        mp = 'head.mmcap.multi_scale.concat_conv.'
+        assert act in ('gelu', 'relu')
         Wc = self._w_plain(mp + '0.weight', L, ctot, 1, 1)
-        ms = self.ms = dict(cat=cat, ctot=ctot, c=self.act('ms.c', (M4, L)), bn=self._bn_bufs(mp + '1.', L), z=self.act('ms.z', (M4, L)))
+        ms = self.ms = dict(cat=cat, ctot=ctot, c=self.act('ms.c', (M4, L)), bn=self._bn_bufs(mp + '1.', L), pre=mp, act=act)
         F.gemm(cat, Wc, ms['c'], M4, L, ctot, dt, ldb=pad8(ctot), colsum=ms['bn']['s'] if T else None,
                colsumsq=ms['bn']['q'] if T else None, label=mp + 'conv')
         self._bn_finalize(mp + '1.', ms['bn'], M4, L)
+        x = ms['x'] = self.buf('ms.x', (M4, L))
+        if act == 'relu':
+            F.affine_act(ms['c'], ms['bn']['scale'], ms['bn']['shift'], None, x, M4, L, True, dt, label=mp + 'bn')
+            return x
+        ms['z'] = self.act('ms.z', (M4, L))
         F.affine_act(ms['c'], ms['bn']['scale'], ms['bn']['shift'], None, ms['z'], M4, L, False, dt, label=mp + 'bn')
-        x = self.buf('ms.x', (M4, L))
         F.gelu_fwd(ms['z'], x, M4 * L, dt, label=mp + 'gelu')
         return x
 
@@ -96,7 +106,8 @@ class MAPEngine(GAEngine):
         # ---- dropout masks (training, p > 0): [attn | proj | mlp] per group in ONE fp32 buffer, refilled every step
         pd, pa = (cfg['head_drop'], cfg['head_attn_drop']) if T else (0.0, 0.0)
         N = Tq + HW
-        n_attn, n_proj, n_mlp = B * Tq * nh * N, B * Tq * L, B * Tq * 4 * L
+        Hm = int(cfg['mlp_ratio'] * L)       # the CABlock MLP's hidden width
+        n_attn, n_proj, n_mlp = B * Tq * nh * N, B * Tq * L, B * Tq * Hm
         self.drop = None
         if T and (pd > 0 or pa > 0):
             assert abs(pd - pa) < 1e-12, 'one keep probability for the whole mask buffer'
@@ -107,7 +118,7 @@ class MAPEngine(GAEngine):
             self.drop['plan'].dropout_mask_sample(buf, buf.numel(), 1.0 - pd, torch.initial_seed() + 0x5eed, self.drop['counter'])
             self.drop['views'] = [dict(attn=buf[k * per:k * per + n_attn].view(B, Tq, nh, N),
                                        proj=buf[k * per + n_attn:k * per + n_attn + n_proj].view(B * Tq, L),
-                                       mlp=buf[k * per + n_attn + n_proj:(k + 1) * per].view(B * Tq, 4 * L)) for k in range(G)]
+                                       mlp=buf[k * per + n_attn + n_proj:(k + 1) * per].view(B * Tq, Hm)) for k in range(G)]
         # ---- the image rows of norm1(cat(x_cls, x_img)) are the same for every group: ONE LayerNorm, ONE stacked k|v GEMM
         tk = self.tok = dict(xn=self.act('ca.tok.xn', (M4, L)), rstd=self.act('ca.tok.rstd', (M4,), torch.float32))
         F.layernorm_fwd(x, None, None, tk['xn'], None, tk['rstd'], M4, L, 1e-6, dt, label='ca.tok.ln')
@@ -121,7 +132,7 @@ class MAPEngine(GAEngine):
         mm = self.mm = cfg['gram_dim'] != L
         self.kv_img, self.n1_img = ('attn.k2', 'norm1_2') if mm else ('attn.k', 'norm1')
         for k in range(G):
-            ap = f'head.mmcap.mmcap.{k}.attention.0.'
+            ap = f'{self.HP}mmcap.mmcap.{k}.attention.0.'
             kn, vn = ap + self.kv_img, ap + self.kv_img.replace('.k', '.v')
             pk, pv, bk, bv = P[kn + '.weight'], P[vn + '.weight'], P[kn + '.bias'], P[vn + '.bias']
             assert pv.data_ptr() == pk.data_ptr() + pk.numel() * 4 and bv.data_ptr() == bk.data_ptr() + bk.numel() * 4, \
@@ -137,7 +148,7 @@ class MAPEngine(GAEngine):
         gc['WT'] = self.buf('wT.ch_reduction.all', (L, G * bp)) if T else None
         gc['s'], gc['q'] = self._bn_pool(G * bp), self._bn_pool(G * bp)
         for k in range(G):
-            gp = f'head.mmcap.mmcap.{k}.gram_token_extraction.'
+            gp = f'{self.HP}mmcap.mmcap.{k}.gram_token_extraction.'
             self.prep.weight_prep(P[gp + 'ch_reduction.0.weight'], 1, bp, L, 1, 1, dt, out=gc['W'][k * bp:], ldo=L,
                                   outT=gc['WT'][:, k * bp:] if T else None, ldt=G * bp if T else 0, t_cols=bp, label='prep.' + gp + 'chr')
         gc['out'] = self.act('ch_reduction.all.out', (M4, G * bp))
@@ -156,11 +167,11 @@ class MAPEngine(GAEngine):
                 fo['bt'] = self.buf('w.fc.org.bt', (G, Tn, NC), torch.float32)
                 wt = [self.buf(f'w.fc.org.split.{k}.{t}', (NC, L)) for t in range(Tn)]      # (weight_prep pads an output row to ldo: it
                 for t in range(Tn):                                                          # cannot write a column slice directly)
-                    self.prep.weight_prep(P[f'head.heads.{k}.head.{t}.weight'], 1, NC, L, 1, 1, dt, out=wt[t], ldo=L,
+                    self.prep.weight_prep(P[f'{self.HP}heads.{k}.head.{t}.weight'], 1, NC, L, 1, 1, dt, out=wt[t], ldo=L,
                                           outT=fo['WT'][k][t * L:] if T else None, ldt=pad8(NC) if T else 0,
-                                          cs=P[f'head.heads.{k}.norm.{t}.weight'], label=f'prep.heads.{k}.{t}')
-                    self.prep.bias_fold(P[f'head.heads.{k}.head.{t}.weight'], P[f'head.heads.{k}.head.{t}.bias'], None,
-                                        P[f'head.heads.{k}.norm.{t}.bias'], fo['bt'][k, t], NC, L)
+                                          cs=P[f'{self.HP}heads.{k}.norm.{t}.weight'], label=f'prep.heads.{k}.{t}')
+                    self.prep.bias_fold(P[f'{self.HP}heads.{k}.head.{t}.weight'], P[f'{self.HP}heads.{k}.head.{t}.bias'], None,
+                                        P[f'{self.HP}heads.{k}.norm.{t}.bias'], fo['bt'][k, t], NC, L)
                 self.prep.flush('prep.split.')
                 for t in range(Tn):
                     self.prep.copy2d(wt[t], L, fo['W'][k][:, t * L:], Tn * L, NC, L, dt, label=f'prep.heads.{k}.{t}.place')
@@ -169,7 +180,7 @@ class MAPEngine(GAEngine):
                     self.prep.axpy_f32(fo['b'][k], fo['bt'][k, t], 1.0, NC)
                     self.prep.flush(f'prep.split.sum{t}.')
                 continue
-            wn = f'head.heads.{k}.weight' if hfn == 'linear' else f'head.heads.{k}.head.weight'
+            wn = f'{self.HP}heads.{k}.weight' if hfn == 'linear' else f'{self.HP}heads.{k}.head.weight'
             self.prep.weight_prep(P[wn], 1, NC, Tn * L, 1, 1, dt, out=fo['W'][k], ldo=Tn * L,
                                   outT=fo['WT'][k] if T else None, ldt=pad8(NC) if T else 0, label=f'prep.heads.{k}')
             self.prep.bias_fold(None, P[wn[:-6] + 'bias'], None, None, fo['b'][k], NC, Tn * L)
@@ -179,9 +190,9 @@ class MAPEngine(GAEngine):
             fa['WT'] = self.buf('wT.fc.avg', (G, L, pad8(NC)))
             fa['b'] = self.buf('w.fc.avg.b', (G, NC), torch.float32)
             for k in range(G):
-                self.prep.weight_prep(P[f'head.self_dt_heads.{k}.head.weight'], 1, NC, L, 1, 1, dt, out=fa['W'][k], ldo=L,
+                self.prep.weight_prep(P[f'{self.HP}self_dt_heads.{k}.head.weight'], 1, NC, L, 1, 1, dt, out=fa['W'][k], ldo=L,
                                       outT=fa['WT'][k], ldt=pad8(NC), label=f'prep.self_dt_heads.{k}')
-                self.prep.bias_fold(None, P[f'head.self_dt_heads.{k}.head.bias'], None, None, fa['b'][k], NC, L)
+                self.prep.bias_fold(None, P[f'{self.HP}self_dt_heads.{k}.head.bias'], None, None, fa['b'][k], NC, L)
         # ---- the groups: independent chains of small launches -> side lanes, own transients
         self.head_lanes = int(os.environ.get('GAEXT_HEAD_STREAMS', '4'))
         self.groups = []
@@ -207,8 +218,8 @@ class MAPEngine(GAEngine):
         R = B * Tq                       # class rows
         h = dict(k=k)
         dm = self.drop['views'][k] if self.drop else {}
-        gp = f'head.mmcap.mmcap.{k}.gram_token_extraction.'
-        ap = f'head.mmcap.mmcap.{k}.attention.0.'
+        gp = f'{self.HP}mmcap.mmcap.{k}.gram_token_extraction.'
+        ap = f'{self.HP}mmcap.mmcap.{k}.attention.0.'
         gcn = self.gcon
         # --- ch_reduction BN on this group's column slice
         h['gc'] = gcn['out'][:, k * bp:]
@@ -300,9 +311,10 @@ class MAPEngine(GAEngine):
         F.layernorm_fwd(h['cls1'], P[ap + 'norm2.weight'], P[ap + 'norm2.bias'], h['t'], h['m2'], h['r2'], R, L, 1e-6, dt,
                         label=ap + 'ln2')
         h['cls2'] = self.buf(ap + 'cls2', (R, L))
-        h['mlp'] = self._gmlp_fwd(ap + 'mlp.', h['t'], R, L, mg, h['cls2'], h['cls1'], None, 1, act='relu', drop_mask=dm.get('mlp'))
+        h['mlp'] = self._gmlp_fwd(ap + 'mlp.', h['t'], R, L, mg, h['cls2'], h['cls1'], None, 1, act='relu', drop_mask=dm.get('mlp'),
+                                  ratio=cfg['mlp_ratio'])
         # --- NormHead inputs: the T gram tokens flattened (heads) / the mean token (self_dt_heads), each LayerNorm-ed (eps 1e-5)
-        hp = f'head.heads.{k}.'
+        hp = f'{self.HP}heads.{k}.'
         if self.head_fn == 'linear':         # nn.Linear on the flattened tokens: no norm
             F.copy2d(h['cls2'], Tq * L, self.fc_org['x'][k], Tn * L, B, Tn * L, dt, label=hp + 'org')
         else:
@@ -316,7 +328,7 @@ class MAPEngine(GAEngine):
                 F.layernorm_fwd(h['org'], P[hp + 'norm.weight'], P[hp + 'norm.bias'], self.fc_org['x'][k], h['om'], h['orr'], B, Tn * L, 1e-5,
                                 dt, label=hp + 'ln')
         if T and self.sdt:
-            sp = f'head.self_dt_heads.{k}.'
+            sp = f'{self.HP}self_dt_heads.{k}.'
             h['avg'] = self.act(sp + 'avg', (B, L))
             F.copy2d(h['cls2'][:, :].view(B, Tq * L)[:, Tn * L:], Tq * L, h['avg'], L, B, L, dt, label=sp + 'avg')
             h['am_'], h['ar'] = self.act(sp + 'm', (B,), torch.float32), self.act(sp + 'r', (B,), torch.float32)
@@ -334,9 +346,9 @@ class MAPEngine(GAEngine):
         hd = E // nh
         R = B * Tq
         dm = self.drop['views'][k] if self.drop else {}
-        gp = f'head.mmcap.mmcap.{k}.gram_token_extraction.'
-        ap = f'head.mmcap.mmcap.{k}.attention.0.'
-        hp, sp = f'head.heads.{k}.', f'head.self_dt_heads.{k}.'
+        gp = f'{self.HP}mmcap.mmcap.{k}.gram_token_extraction.'
+        ap = f'{self.HP}mmcap.mmcap.{k}.attention.0.'
+        hp, sp = f'{self.HP}heads.{k}.', f'{self.HP}self_dt_heads.{k}.'
         # --- NormHeads -> gradient wrt cls2 [B][Tq][L]
         dcls2 = self.tmp('dcls2', (R, L))
         if self.head_fn == 'linear':
@@ -460,13 +472,13 @@ class MAPEngine(GAEngine):
             for k in range(G):
                 if name == 'heads' and hfn == 'split':      # undo the LayerNorm fold per token: dW_t, d(bias_t), d(gamma_t), d(beta_t)
                     for t in range(Tn):
-                        hk = f'head.heads.{k}.'
-                        Bk.weight_unfold(Gfc[k][:, t * L:], Tn * L, NC, L, gb=gbfc[k], W=P[hk + f'head.{t}.weight'], b=P[hk + f'head.{t}.bias'],
-                                         cs=P[hk + f'norm.{t}.weight'], v=P[hk + f'norm.{t}.bias'], dW=self.grad(hk + f'head.{t}.weight'),
-                                         db=self.grad(hk + f'head.{t}.bias'), d_cs=self.grad(hk + f'norm.{t}.weight'),
+                        hk = f'{self.HP}heads.{k}.'
+                        Bk.weight_unfold(Gfc[k][:, t * L:], Tn * L, NC, L, gb=gbfc[k], W=P[hk + f'{self.HP}{t}.weight'], b=P[hk + f'{self.HP}{t}.bias'],
+                                         cs=P[hk + f'norm.{t}.weight'], v=P[hk + f'norm.{t}.bias'], dW=self.grad(hk + f'{self.HP}{t}.weight'),
+                                         db=self.grad(hk + f'{self.HP}{t}.bias'), d_cs=self.grad(hk + f'norm.{t}.weight'),
                                          d_v=self.grad(hk + f'norm.{t}.bias'), label=hk + f'{t}.unf')
                     continue
-                wn = f'head.{name}.{k}.weight' if (name == 'heads' and hfn == 'linear') else f'head.{name}.{k}.head.weight'
+                wn = f'{self.HP}{name}.{k}.weight' if (name == 'heads' and hfn == 'linear') else f'{self.HP}{name}.{k}.head.weight'
                 Bk.axpy_f32(self.grad(wn), Gfc[k], 1.0, NC * cin)
                 Bk.axpy_f32(self.grad(wn[:-6] + 'bias'), gbfc[k], 1.0, NC)
             fc['dx'] = self.tmp(f'dfc.{name}', (G, B, cin))
@@ -487,7 +499,7 @@ class MAPEngine(GAEngine):
         with self._wlane():
             Bk.wgrad(gcn['dout'], x, Gc, M4, gcn['ld'], L, dt, label='ch_reduction.all.wg')
         for k in range(G):
-            Bk.axpy_f32(self.grad(f'head.mmcap.mmcap.{k}.gram_token_extraction.ch_reduction.0.weight'), Gc[k * bp:], 1.0, bp * L)
+            Bk.axpy_f32(self.grad(f'{self.HP}mmcap.mmcap.{k}.gram_token_extraction.ch_reduction.0.weight'), Gc[k * bp:], 1.0, bp * L)
         dx = self.tmp('dx_ms', (M4, L))
         Bk.gemm(gcn['dout'], gcn['WT'], dx, M4, L, gcn['ld'], dt, label='ch_reduction.all.dg')
         # image rows of all groups: effective k|v weight gradients, each group's norm1 fold undone; dx += LN'(...)
@@ -495,7 +507,7 @@ class MAPEngine(GAEngine):
         with self._wlane():
             Bk.wgrad(tk['dkv'], tk['xn'], tk['G'], M4, tk['ld'], L, dt, dbias=tk['gb'], label='ca.kv_all.wg')
         for k in range(G):
-            ap = f'head.mmcap.mmcap.{k}.attention.0.'
+            ap = f'{self.HP}mmcap.mmcap.{k}.attention.0.'
             kn, nn_ = ap + self.kv_img, ap + self.n1_img
             Bk.weight_unfold(tk['G'][k * E2:], L, E2, L, gb=tk['gb'][k * E2:], W=P[kn + '.weight'], b=P[kn + '.bias'],
                              cs=P[nn_ + '.weight'], v=P[nn_ + '.bias'], dW=self.grad(kn + '.weight'),
@@ -504,13 +516,16 @@ class MAPEngine(GAEngine):
         dxt = self.tmp('dxn_tok', (M4, L))
         Bk.gemm(tk['dkv'], tk['WT'], dxt, M4, L, tk['ld'], dt, label='ca.kv_all.dg')
         Bk.layernorm_bwd(dxt, tk['xn'], None, tk['rstd'], None, dx, dx, None, None, M4, L, True, dt, label='ca.tok.lnb')
-        # MultiScale: GELU, BN, conv1x1
+        # MultiScale (or channel_convertor): activation, BN, conv1x1
         ms = self.ms
-        mp = 'head.mmcap.multi_scale.concat_conv.'
-        dz = self.tmp('dz_ms', (M4, L))
-        Bk.gelu_bwd(dx, ms['z'], dz, M4 * L, dt, label=mp + 'gelub')
+        mp = ms['pre']
         dc = self.tmp('dc_ms', (M4, L))
-        self._bn_bwd(mp + '1.', ms['bn'], dz, None, ms['c'], dc, M4, L)
+        if ms['act'] == 'relu':      # ReLU backward as the BN backward's mask on the stored output
+            self._bn_bwd(mp + '1.', ms['bn'], dx, ms['x'], ms['c'], dc, M4, L)
+        else:
+            dz = self.tmp('dz_ms', (M4, L))
+            Bk.gelu_bwd(dx, ms['z'], dz, M4 * L, dt, label=mp + 'gelub')
+            self._bn_bwd(mp + '1.', ms['bn'], dz, None, ms['c'], dc, M4, L)
         ctot = ms['ctot']
         with self._wlane():
             Bk.wgrad(dc, ms['cat'], self.grad(mp + '0.weight'), M4, L, ctot, dt, label=mp + 'wg')

@@ -119,9 +119,13 @@ class _MAPHead(Holder):
         L, G, T = cfg['last_dim'], cfg['n_groups'], cfg['n_tokens']
         self.mmcap = Holder()
         self.mmcap.mmcap = nn.ModuleList([_CAP(cfg) for _ in range(G)])
-        ms = Holder()
-        ms.concat_conv = nn.Sequential(nn.Conv2d(sum(channels), L, 1, bias=False), nn.BatchNorm2d(L))
-        self.mmcap.multi_scale = ms
+        if cfg.get('channel_convertor', False):
+            # multi_scale_level = -1 and last_dim != channels[-1] (map.py:356-364): ConvNormAct(channels[-1], last_dim, 1) on the last map
+            self.mmcap.channel_convertor = nn.Sequential(nn.Conv2d(channels[-1], L, 1, bias=False), nn.BatchNorm2d(L))
+        else:
+            ms = Holder()
+            ms.concat_conv = nn.Sequential(nn.Conv2d(sum(channels), L, 1, bias=False), nn.BatchNorm2d(L))
+            self.mmcap.multi_scale = ms
         hfn = cfg.get('head_fn', 'norm')
         if hfn == 'split':
             self.heads = nn.ModuleList([_SplitNormHead(L * T, cfg['num_classes'], T) for _ in range(G)])

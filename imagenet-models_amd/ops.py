@@ -537,6 +537,28 @@ class Plan:
         self._add('ga_dwconv7_bwd_weight', head + box.get('ws', (None, 0)), label, keep=(dy, x, dw49, dbias))
         box['idx'] = len(self.calls) - 1
 
+    def dwconv3_fwd(self, x, w9, y, B, H, W, Cdim, stride, dtype, colsum=None, colsumsq=None, label=None):
+        self._add('ga_dwconv3_fwd', (_ptr(x), _ptr(w9), _ptr(y), B, H, W, Cdim, stride, _ptr(colsum), _ptr(colsumsq), dtype), label,
+                  keep=(x, w9, y, colsum, colsumsq))
+
+    def dwconv3_bwd_data(self, dy, w9, dx, B, H, W, Cdim, stride, dtype, label=None):
+        self._add('ga_dwconv3_bwd_data', (_ptr(dy), _ptr(w9), _ptr(dx), B, H, W, Cdim, stride, dtype), label, keep=(dy, w9, dx))
+
+    def dwconv3_bwd_weight(self, dy, x, dw9, B, H, W, Cdim, stride, dtype, label=None):
+        """dw9 [C][9] += the weight gradient; per-workgroup partials in this plan's per-lane workspace (see dwconv7_bwd_weight)"""
+        need = int(self.lib.ga_dwconv3_bwd_weight_workspace(B, H, W, Cdim, stride, dtype))
+        head = (_ptr(dy), _ptr(x), _ptr(dw9), B, H, W, Cdim, stride, dtype)
+        box = {}
+
+        def patch(ptr, nbytes):
+            box['ws'] = (ptr, nbytes)
+            if 'idx' in box:
+                fn, _, lb = self.calls[box['idx']]
+                self.calls[box['idx']] = (fn, head + (ptr, nbytes), lb)
+        self._want_workspace(need, patch)
+        self._add('ga_dwconv3_bwd_weight', head + box.get('ws', (None, 0)), label, keep=(dy, x, dw9))
+        box['idx'] = len(self.calls) - 1
+
     def layernorm_fwd(self, x, w, b, y, mean, rstd, rows, Cdim, eps, dtype, label=None):
         self._add('ga_layernorm_fwd', (_ptr(x), _ptr(w), _ptr(b), _ptr(y), _ptr(mean), _ptr(rstd), rows, Cdim, eps, dtype),
                   label, keep=(x, w, b, y, mean, rstd))

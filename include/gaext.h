@@ -217,6 +217,24 @@ int ga_dwconv7_bwd_weight(const void* dy, const void* x, float* dw49, float* dbi
                           int dtype, void* workspace, size_t ws_bytes, ga_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Depthwise 3x3 (pad 1, stride 1 or 2, no bias) convolution, NHWC [B][H][W][C] -> [B][Ho][Wo][C], Ho = (H - 1) / stride + 1
+ * (MobileNetV1's conv_dw, MAP/models/map_mobilenet.py:27-38).  w9: fp32 [C][9], the (C, 1, 3, 3) parameter as it is.
+ * C % 8 == 0 and stride in {1, 2} (GA_ERR_UNSUPPORTED otherwise); H, W any size >= 1.
+ *   fwd:        colsum / colsumsq (both or neither) accumulate sum_rows y and sum_rows y^2 of the fp32 outputs before rounding
+ *               (the batch statistics of the BatchNorm that follows; one atomic per channel per workgroup)
+ *   bwd_data:   dx (H x W, overwritten) from dy (Ho x Wo): gather form, no atomics
+ *   bwd_weight: dw9[C][9] += sum dy * shifted x; per-workgroup partials in the CALLER-provided workspace of
+ *               ga_dwconv3_bwd_weight_workspace(...) bytes, then one reduction launch (deterministic for a fixed shape)
+ * ------------------------------------------------------------------------------------------------------------ */
+int ga_dwconv3_fwd(const void* x, const float* w9, void* y, int B, int H, int W, int C, int stride, float* colsum,
+                   float* colsumsq, int dtype, ga_stream_t stream);
+int ga_dwconv3_bwd_data(const void* dy, const float* w9, void* dx, int B, int H, int W, int C, int stride, int dtype,
+                        ga_stream_t stream);
+size_t ga_dwconv3_bwd_weight_workspace(int B, int H, int W, int C, int stride, int dtype);
+int ga_dwconv3_bwd_weight(const void* dy, const void* x, float* dw9, int B, int H, int W, int C, int stride, int dtype,
+                          void* workspace, size_t ws_bytes, ga_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * LayerNorm over the last dim of [rows][C]  (F.layer_norm / LayerNorm2d, ga_convnext.py:51-67,93,233,237)
  *   fwd: y = (x-mean)*rstd [*w + b];  saves mean/rstd fp32 [rows] (each may be NULL).
  *   bwd: xhat = x_is_normalized ? x : (x-mean)*rstd;
