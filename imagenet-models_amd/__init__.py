@@ -24,6 +24,8 @@ from .convnext import ConvNeXt  # noqa: E402,F401
 from .map_pit import MAP_PiT  # noqa: E402,F401
 from . import mobilenet  # noqa: E402,F401  (registers the extra names mobilenet_v1 / map_mobilenet_v1)
 from .mobilenet import MobileNetV1  # noqa: E402,F401
+from . import map_resnet  # noqa: E402,F401  (registers the repaired name map_resnet50)
+from .map_resnet import MAP_ResNet  # noqa: E402,F401
 from .loss import ga_loss, heads_topk, accuracy_from_topk, map_loss, heads_mean_topk  # noqa: E402,F401
 from .optim import create_optimizer_v2, FusedSGD, FusedAdamW, FusedLamb, CosineLRScheduler  # noqa: E402,F401
 from .mixup import Mixup  # noqa: E402,F401

@@ -125,6 +125,20 @@ _SIGS = {
     'ga_dwconv3_bwd_data': ([vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
     'ga_dwconv3_bwd_weight': ([vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, C.c_size_t, vp], i32),
     'ga_dwconv3_bwd_weight_workspace': ([i32, i32, i32, i32, i32, i32], C.c_size_t),
+    'ga_maxpool3s2_fwd': ([vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
+    'ga_maxpool3s2_bwd': ([vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
+    'ga_bn_gelu_fwd': ([vp, vp, vp, vp, i64, i32, i32, vp], i32),
+    'ga_bn_gelu_bwd_workspace': ([i64, i32], C.c_size_t),
+    'ga_bn_gelu_bwd_reduce': ([vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, C.c_size_t, vp], i32),
+    'ga_bn_gelu_bwd_apply': ([vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, i32, i32, vp], i32),
+    'ga_se_bn_fwd': ([vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp], i32),
+    'ga_se_bn_bwd': ([vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                      vp, vp, i32, i32, i32, vp], i32),
+    'ga_se_residual_fwd': ([vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp], i32),
+    'ga_se_residual_bwd_a': ([vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp], i32),
+    'ga_se_residual_bwd_b': ([vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp], i32),
+    'ga_subsample2_fwd': ([vp, vp, i32, i32, i32, i32, i32, vp], i32),
+    'ga_subsample2_bwd': ([vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
     'ga_wgrad_workspace': ([C.POINTER(WgradDesc)], C.c_size_t),
     'ga_layernorm_fwd': ([vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp], i32),
     'ga_layernorm_bwd': ([vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp], i32),

@@ -559,6 +559,63 @@ class Plan:
         self._add('ga_dwconv3_bwd_weight', head + box.get('ws', (None, 0)), label, keep=(dy, x, dw9))
         box['idx'] = len(self.calls) - 1
 
+    # -- MAP-ResNet50 (csrc/resnet.hip) --------------------------------------------------------------
+    def maxpool3s2_fwd(self, x, y, idx, B, H, W, Cdim, dtype, label=None):
+        self._add('ga_maxpool3s2_fwd', (_ptr(x), _ptr(y), _ptr(idx), B, H, W, Cdim, dtype), label, keep=(x, y, idx))
+
+    def maxpool3s2_bwd(self, dy, idx, dx, B, H, W, Cdim, dtype, accumulate=False, label=None):
+        self._add('ga_maxpool3s2_bwd', (_ptr(dy), _ptr(idx), _ptr(dx), B, H, W, Cdim, int(accumulate), dtype), label, keep=(dy, idx, dx))
+
+    def bn_gelu_fwd(self, x, scale, shift, y, rows, Cdim, dtype, label=None):
+        self._add('ga_bn_gelu_fwd', (_ptr(x), _ptr(scale), _ptr(shift), _ptr(y), rows, Cdim, dtype), label, keep=(x, scale, shift, y))
+
+    def bn_gelu_bwd_reduce(self, dy, x, scale, shift, mean, rstd, s1, s2, rows, Cdim, dtype, label=None):
+        """s1 / s2 (overwritten) = sum g, sum g * xhat with g = dy * gelu'(x * scale + shift); partials in this plan's per-lane workspace"""
+        need = int(self.lib.ga_bn_gelu_bwd_workspace(rows, Cdim))
+        head = (_ptr(dy), _ptr(x), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd), _ptr(s1), _ptr(s2), rows, Cdim, dtype)
+        box = {}
+
+        def patch(ptr, nbytes):
+            box['ws'] = (ptr, nbytes)
+            if 'idx' in box:
+                fn, _, lb = self.calls[box['idx']]
+                self.calls[box['idx']] = (fn, head + (ptr, nbytes), lb)
+        self._want_workspace(need, patch)
+        self._add('ga_bn_gelu_bwd_reduce', head + box.get('ws', (None, 0)), label, keep=(dy, x, scale, shift, mean, rstd, s1, s2))
+        box['idx'] = len(self.calls) - 1
+
+    def bn_gelu_bwd_apply(self, dy, x, scale, shift, mean, rstd, w, s1, s2, n, dx, rows, Cdim, dtype, label=None):
+        self._add('ga_bn_gelu_bwd_apply', (_ptr(dy), _ptr(x), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(s1), _ptr(s2), n,
+                                           _ptr(dx), rows, Cdim, dtype), label, keep=(dy, x, scale, shift, mean, rstd, w, s1, s2, dx))
+
+    def se_bn_fwd(self, S, HW, scale3, shift3, W1, g1, b1, rmean, rvar, W2, b2, hpre, mean, rstd, h, gate, B, Cdim, R, training, label=None):
+        args = (S, scale3, shift3, W1, g1, b1, rmean, rvar, W2, b2, hpre, mean, rstd, h, gate)
+        self._add('ga_se_bn_fwd', (_ptr(S), HW) + tuple(_ptr(t) for t in args[1:]) + (B, Cdim, R, int(training)), label, keep=args)
+
+    def se_bn_bwd(self, P1, P2, rowscale, g3, b3, mean3, rstd3, S, HW, scale3, shift3, W1, g1, b1, W2, hpre, mean, rstd, h, gate, dz, dhpre,
+                  ds, s1, s2, dW1, dg1, db1, dW2, db2, B, Cdim, R, label=None):
+        pre = (P1, P2, rowscale, g3, b3, mean3, rstd3, S)
+        post = (scale3, shift3, W1, g1, b1, W2, hpre, mean, rstd, h, gate, dz, dhpre, ds, s1, s2, dW1, dg1, db1, dW2, db2)
+        self._add('ga_se_bn_bwd', tuple(_ptr(t) for t in pre) + (HW,) + tuple(_ptr(t) for t in post) + (B, Cdim, R), label, keep=pre + post)
+
+    def se_residual_fwd(self, x3, scale3, shift3, gate, rowscale, res, rscale, rshift, y, B, HW, Cdim, dtype, label=None):
+        args = (x3, scale3, shift3, gate, rowscale, res, rscale, rshift, y)
+        self._add('ga_se_residual_fwd', tuple(_ptr(t) for t in args) + (B, HW, Cdim, dtype), label, keep=args)
+
+    def se_residual_bwd_a(self, dy, y, x3, mean3, rstd3, dm, P1, P2, B, HW, Cdim, dtype, label=None):
+        args = (dy, y, x3, mean3, rstd3, dm, P1, P2)
+        self._add('ga_se_residual_bwd_a', tuple(_ptr(t) for t in args) + (B, HW, Cdim, dtype), label, keep=args)
+
+    def se_residual_bwd_b(self, dm, x3, mean3, rstd3, g3, gate, rowscale, ds, s1, s2, dx3, B, HW, Cdim, dtype, label=None):
+        args = (dm, x3, mean3, rstd3, g3, gate, rowscale, ds, s1, s2, dx3)
+        self._add('ga_se_residual_bwd_b', tuple(_ptr(t) for t in args) + (B, HW, Cdim, dtype), label, keep=args)
+
+    def subsample2_fwd(self, x, y, B, H, W, Cdim, dtype, label=None):
+        self._add('ga_subsample2_fwd', (_ptr(x), _ptr(y), B, H, W, Cdim, dtype), label, keep=(x, y))
+
+    def subsample2_bwd(self, dy, dx, B, H, W, Cdim, dtype, accumulate=False, label=None):
+        self._add('ga_subsample2_bwd', (_ptr(dy), _ptr(dx), B, H, W, Cdim, int(accumulate), dtype), label, keep=(dy, dx))
+
     def layernorm_fwd(self, x, w, b, y, mean, rstd, rows, Cdim, eps, dtype, label=None):
         self._add('ga_layernorm_fwd', (_ptr(x), _ptr(w), _ptr(b), _ptr(y), _ptr(mean), _ptr(rstd), rows, Cdim, eps, dtype),
                   label, keep=(x, w, b, y, mean, rstd))

@@ -235,6 +235,60 @@ int ga_dwconv3_bwd_weight(const void* dy, const void* x, float* dw9, int B, int 
                           void* workspace, size_t ws_bytes, ga_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * MAP-ResNet50 (MAP/models/map_resnet.py): NHWC, C % 8 == 0 (GA_ERR_UNSUPPORTED otherwise), bf16 / fp32 tensors, fp32 math.
+ *   maxpool3s2_fwd:  MaxPool2d(3, 2, 1), any H, W; Ho = (H - 1) / 2 + 1.  PyTorch's rule: the first maximum in row-major window order,
+ *                    NaN propagates.  idx (uint8 [B][Ho][Wo][C], window tap 0..8, may be NULL) feeds the backward.
+ *   maxpool3s2_bwd:  dx (H x W) = (accumulate ? dx : 0) + the gradients of the outputs that chose each pixel (gather, no atomics)
+ *   bn_gelu_fwd:     y = gelu_erf(x * scale[c] + shift[c])
+ *   bn_gelu_bwd_reduce: g = dy * gelu'(x * scale + shift), xhat = (x - mean) * rstd; s1[c] = sum g, s2[c] = sum g * xhat (overwritten);
+ *                    per-workgroup partials in the caller's workspace of ga_bn_gelu_bwd_workspace(rows, C) bytes, then one ordered
+ *                    reduction (deterministic)
+ *   bn_gelu_bwd_apply: dx = w * rstd * (g - s1 / n - xhat * s2 / n)   (w NULL -> 1)
+ *   se_bn_fwd:       SEUnit with BatchNorm (B <= 1024, C <= 2048, R <= 128; train mode needs B >= 2).  S [B][C] = sum_hw of the raw
+ *                    conv output, p = scale3 * S / HW + shift3; hpre = p W1^T (W1 [R][C], no bias); BatchNorm (g1, b1, eps 1e-5)
+ *                    over the B rows: batch statistics and the running-stat update (momentum 0.1, unbiased variance) when
+ *                    training, the running statistics otherwise (mean / rstd [R] written either way); h = gelu(.);
+ *                    gate = sigmoid(h W2^T + b2) (W2 [C][R]).  All fp32.
+ *   se_bn_bwd:       from P1 / P2 [B][C] of se_residual_bwd_a: dgate = r * (g3 P2 + b3 P1); writes dz [B][C] and dhpre [B][R]
+ *                    (workspaces), ds [B][C] (the gradient of p) and the BatchNorm-3 sums s1 / s2 [C] (overwritten); dW1, dg1, db1,
+ *                    dW2, db2 are accumulated (+=) with one owner per element (no atomics)
+ *   se_residual_fwd: y = relu(res' + r[b] * gate[b][c] * (x3 * scale3 + shift3)); res' = res * rscale + rshift, or res when both are
+ *                    NULL; r = rowscale (DropPath factors, NULL -> 1)
+ *   se_residual_bwd_a: dm = dy * (y > 0) (also the residual's gradient); P1 = sum_hw dm, P2 = sum_hw dm * xhat3 per (b, c), one
+ *                    workgroup per (sample, channel chunk): no atomics
+ *   se_residual_bwd_b: dx3 = g3 * rstd3 * (du - s1 / n - xhat3 * s2 / n), du = dm * gate * r + ds / HW, n = B * HW
+ *   subsample2_fwd / _bwd: y[b, oy, ox] = x[b, 2oy, 2ox] (the input of a 1 x 1 / 2 conv, Ho = (H - 1) / 2 + 1); the backward writes
+ *                    the zero-filled transpose, or adds into dx at the even pixels when accumulate
+ * ------------------------------------------------------------------------------------------------------------ */
+int ga_maxpool3s2_fwd(const void* x, void* y, unsigned char* idx, int B, int H, int W, int C, int dtype, ga_stream_t stream);
+int ga_maxpool3s2_bwd(const void* dy, const unsigned char* idx, void* dx, int B, int H, int W, int C, int accumulate, int dtype,
+                      ga_stream_t stream);
+int ga_bn_gelu_fwd(const void* x, const float* scale, const float* shift, void* y, int64_t rows, int C, int dtype, ga_stream_t stream);
+size_t ga_bn_gelu_bwd_workspace(int64_t rows, int C);
+int ga_bn_gelu_bwd_reduce(const void* dy, const void* x, const float* scale, const float* shift, const float* mean, const float* rstd,
+                          float* s1, float* s2, int64_t rows, int C, int dtype, void* workspace, size_t ws_bytes, ga_stream_t stream);
+int ga_bn_gelu_bwd_apply(const void* dy, const void* x, const float* scale, const float* shift, const float* mean, const float* rstd,
+                         const float* w, const float* s1, const float* s2, int64_t n, void* dx, int64_t rows, int C, int dtype,
+                         ga_stream_t stream);
+int ga_se_bn_fwd(const float* S, int HW, const float* scale3, const float* shift3, const float* W1, const float* g1, const float* b1,
+                 float* rmean, float* rvar, const float* W2, const float* b2, float* hpre, float* mean, float* rstd, float* h, float* gate,
+                 int B, int C, int R, int training, ga_stream_t stream);
+int ga_se_bn_bwd(const float* P1, const float* P2, const float* rowscale, const float* g3, const float* b3, const float* mean3,
+                 const float* rstd3, const float* S, int HW, const float* scale3, const float* shift3, const float* W1, const float* g1,
+                 const float* b1, const float* W2, const float* hpre, const float* mean, const float* rstd, const float* h,
+                 const float* gate, float* dz, float* dhpre, float* ds, float* s1, float* s2, float* dW1, float* dg1, float* db1,
+                 float* dW2, float* db2, int B, int C, int R, ga_stream_t stream);
+int ga_se_residual_fwd(const void* x3, const float* scale3, const float* shift3, const float* gate, const float* rowscale, const void* res,
+                       const float* rscale, const float* rshift, void* y, int B, int HW, int C, int dtype, ga_stream_t stream);
+int ga_se_residual_bwd_a(const void* dy, const void* y, const void* x3, const float* mean3, const float* rstd3, void* dm, float* P1,
+                         float* P2, int B, int HW, int C, int dtype, ga_stream_t stream);
+int ga_se_residual_bwd_b(const void* dm, const void* x3, const float* mean3, const float* rstd3, const float* g3, const float* gate,
+                         const float* rowscale, const float* ds, const float* s1, const float* s2, void* dx3, int B, int HW, int C,
+                         int dtype, ga_stream_t stream);
+int ga_subsample2_fwd(const void* x, void* y, int B, int H, int W, int C, int dtype, ga_stream_t stream);
+int ga_subsample2_bwd(const void* dy, void* dx, int B, int H, int W, int C, int accumulate, int dtype, ga_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * LayerNorm over the last dim of [rows][C]  (F.layer_norm / LayerNorm2d, ga_convnext.py:51-67,93,233,237)
  *   fwd: y = (x-mean)*rstd [*w + b];  saves mean/rstd fp32 [rows] (each may be NULL).
  *   bwd: xhat = x_is_normalized ? x : (x-mean)*rstd;
