@@ -4,6 +4,9 @@
                                       top-5 of a B = 2 eval forward
   tests/golden/map_rn50_train_b4.npz  one train step at B = 4, 224 x 224, fp32: loss, logits, per-tensor gradient norm / sum / first 16
                                       elements, and the running statistics after the step
+  tests/golden/map_rn50_train_b4_fp64.npz  (--fp64) the same train step with the reference classes in float64 (m.double()): the
+                                      fields of oracle/gen_golden_fp64.py -- loss, 40 logits per row, per-tensor gradient norm / sum /
+                                      max |.| / first 16 values -- the ground truth tests/test_map_resnet_gpu.py gates the fp32 engine on
 
 Same recipe as tools/gen_golden_mobilenet.py: the name-hashed fill of tests/_mnv1_state.py over the reference module's own state_dict,
 every nn.Dropout at p = 0, eval running statistics from one train-mode reference forward with momentum 1 (a B = 4 batch of its own),
@@ -15,7 +18,8 @@ and raises IndexError.  The fixtures use the composition the checkp
     stem = m.stem(x); x = m.max_pool(stem); features = [stem, layer1(x), layer2(.), layer3(.), layer4(.)]; m.head(features)
 
 Run (needs the reference tree and its timm stub; not part of the test suite):
-    python tools/gen_golden_map_resnet.py /path/to/reference/MAP/models"""
+    python tools/gen_golden_map_resnet.py /path/to/reference/MAP/models
+    python tools/gen_golden_map_resnet.py --fp64 /path/to/reference/MAP/models"""
 import os
 import sys
 
@@ -128,6 +132,37 @@ def run(ref):
                         running_sum=np.array([float(v.double().sum()) for v in rvals]), running_head=rhead)
 
 
+def run_fp64(ref):
+    """the train step of run() in float64: same fill, input, target and loss; the state is filled in fp32 and widened"""
+    m, _ = build(ref)
+    m.double().train()
+    B, nlog = 4, 40
+    x = gen_input(B, seed=1).double()
+    target = torch.randint(0, 1000, (B,), generator=torch.Generator().manual_seed(99))
+    out = forward_f10(m, x)
+    lg = logits_of(out).detach()
+    loss = ref_loss(out, target, -0.8)
+    loss.backward()
+    grads = {n: p.grad.detach() for n, p in m.named_parameters()}
+    assert loss.dtype == torch.float64 and lg.dtype == torch.float64 and all(g.dtype == torch.float64 for g in grads.values())
+    names = list(grads)
+    head = np.zeros((len(names), 16))
+    for i, n in enumerate(names):
+        f = grads[n].reshape(-1)[:16]
+        head[i, :f.numel()] = f.numpy()
+    print(f'[{TAG}] fp64 train B={B}: loss {float(loss.detach()):.12f}, {len(names)} gradient tensors')
+    np.savez_compressed(os.path.join(OUT, f'{TAG}_train_b4_fp64.npz'), batch=B, dec_lam=-0.8, target=target.numpy(), loss=float(loss.detach()),
+                        logits=lg[:, :, :nlog].numpy(), grad_names=np.array(names),
+                        grad_norm=np.array([float(grads[n].norm()) for n in names]),
+                        grad_sum=np.array([float(grads[n].sum()) for n in names]),
+                        grad_absmax=np.array([float(grads[n].abs().max()) for n in names]), grad_head=head)
+
+
 if __name__ == '__main__':
     torch.manual_seed(0)
-    run(load_reference(sys.argv[1] if len(sys.argv) > 1 else os.environ.get('MAP_MODELS_DIR', '')))
+    args = [a for a in sys.argv[1:] if a != '--fp64']
+    ref = load_reference(args[0] if args else os.environ.get('MAP_MODELS_DIR', ''))
+    if '--fp64' in sys.argv[1:]:
+        run_fp64(ref)
+    else:
+        run(ref)
