@@ -215,3 +215,6 @@ size_t ga_conv3_c64_wgrad_workspace(const ga_wgrad_desc* d);
 int ga_conv3_c64_wgrad_try(const ga_wgrad_desc* d, hipStream_t s);
 int ga_conv3s2_c64_wgrad_try(const ga_wgrad_desc* d, hipStream_t s);
 int ga_conv0_c8_wgrad_try(const ga_wgrad_desc* d, hipStream_t s);
+// ... and the direct form of ga_wgrad's GA_A_STEM4_NCHW product (ConvNeXt stem): bytes of per-workgroup partials / the launch
+size_t ga_stem4_wgrad_workspace(const ga_wgrad_desc* d);
+int ga_stem4_wgrad_try(const ga_wgrad_desc* d, hipStream_t s);

@@ -840,6 +840,174 @@ __global__ __launch_bounds__(256) void stem4_ln_kernel(const float* __restrict__
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Weight gradient of the ConvNeXt stem (Conv2d(3, C, 4, 4), C = 16 NT = 96 / 128): dW[C][48] = sum over the B x H/4 x W/4 output
+// pixels of dpre[m][:]^T patch(m)[48] (k = (c, ky, kx)), + the bias gradient (column sums of dpre).  A streaming reduction: the fp32
+// NCHW image and the bf16 `dpre` are read once (154 + 154 MB at batch 256, C = 96), its 7.4 GFLOP are nothing; the gather form of
+// gemm_tn re-fetched every patch per output tile through per-element address arithmetic and committed with fp32 atomics.
+//   workgroup = 4 waves, persistent over tiles of 128 pixels; a wave owns 32 pixels of the tile and the WHOLE [C][48] result in
+//   registers (3 NT accumulators).  Per step it loads its 32 x C block of dpre (contiguous) and, per lane, one float4 = the 4 kx of
+//   one (c, ky) patch row of one pixel (32 lanes = 32 neighbouring pixels = 512 contiguous bytes), one tile ahead in registers;
+//   packs the image to bf16 and writes both as [pixel][column] images into its own LDS piece (row pitches of 2 C + 32 and 112 bytes:
+//   the 4 rows a transposing read touches fall into different banks); both MFMA operands are contracted over the pixel, so both are
+//   `ds_read_b64_tr_b16` fragments.  The waves add their results in LDS in wave order -> one fp32 partial [C][48] + [C] per
+//   workgroup; stem4_wgrad_reduce sums the partials in a fixed order.  No atomics: two runs give the same bits.
+// ------------------------------------------------------------------------------------------------
+constexpr int S4W_XP = 112;                                   // LDS row pitch of the packed patch image (48 bf16 = 96 B + 16)
+template <int NT> struct S4W {
+    static constexpr int N = 16 * NT;
+    static constexpr int YP = 2 * N + 32;                     // LDS row pitch of the dpre image
+    static constexpr int WAVE = 32 * YP + 32 * S4W_XP;        // 10752 / 12800 bytes per wave
+    static constexpr int LDS = 4 * WAVE;
+    static constexpr int PART = N * 49;                       // floats per partial: [N][48] + [N]
+};
+
+template <int NT>
+__global__ __launch_bounds__(256, 2) void stem4_wgrad_kernel(const bf16_t* __restrict__ dy, const float* __restrict__ x,
+                                                             float* __restrict__ part, int M, int H, int W, int want_bias) {
+    using P = S4W<NT>;
+    constexpr int N = P::N, YP = P::YP, XP = S4W_XP, CPR = N / 8;  // CPR: 16-byte chunks per dpre row
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    unsigned char* ys = smem + wv * P::WAVE;
+    unsigned char* xs = ys + 32 * YP;
+    const unsigned OH = (unsigned)H >> 2, OW = (unsigned)W >> 2;
+    const int ntiles = (M + 127) / 128;
+    const int px = lane & 31, hi = lane >> 5;                  // this lane's pixel of the step; patch rows ky = 2 (i & 1) + hi
+
+    c3_u4 ry[NT];                                              // chunk j = lane + 64 i of the wave's 32 x N block of dpre
+    float4 rx[6];                                              // (c, ky) = (i >> 1, 2 (i & 1) + hi) of pixel px
+    auto g_load = [&](int t) __attribute__((always_inline)) {
+        const int m0 = t * 128 + wv * 32;
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            const int j = lane + 64 * i, row = j / CPR;
+            ry[i] = c3_u4{0u, 0u, 0u, 0u};
+            if (m0 + row < M) ry[i] = *reinterpret_cast<const c3_u4*>(dy + (long)m0 * N + j * 8);
+        }
+        const int m = m0 + px;
+        const bool live = m < M;
+        const unsigned mm = live ? (unsigned)m : 0u;
+        const unsigned t2 = mm / OW, ox = mm - t2 * OW, b = t2 / OH, oy = t2 - b * OH;
+        const float* src = x + ((long)b * 3 * H + 4 * oy + hi) * W + 4 * ox;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            rx[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (live) rx[i] = *reinterpret_cast<const float4*>(src + ((long)(i >> 1) * H + 2 * (i & 1)) * W);
+        }
+    };
+    auto s_store = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            const int j = lane + 64 * i, row = j / CPR, ch = j - row * CPR;
+            *reinterpret_cast<c3_u4*>(ys + row * YP + ch * 16) = ry[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+            *reinterpret_cast<uint2*>(xs + px * XP + (2 * i + hi) * 8) = make_uint2(pack2bf(rx[i].x, rx[i].y), pack2bf(rx[i].z, rx[i].w));
+    };
+
+    // fragment of 16 columns from column 16 t, k step = the wave's 32 pixels: rows 8 (lane >> 4) + 4 hf + ((lane & 15) >> 2)
+    const int frow = 8 * (lane >> 4) + ((lane & 15) >> 2), fsub = ((lane & 3) >> 1) * 16 + 8 * (lane & 1);
+    f32x4_t acc[NT][3];
+    float bsum[NT];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+        bsum[i] = 0.f;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    }
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+    const bf16x2_t ones2 = {(__bf16)1.0f, (__bf16)1.0f};
+
+    int t = blockIdx.x;
+    if (t < ntiles) g_load(t);
+    for (; t < ntiles; t += gridDim.x) {
+        s_store();
+        __syncthreads();                                       // (the pieces are wave-private: orders this wave's writes and reads)
+        if (t + (int)gridDim.x < ntiles) g_load(t + gridDim.x);
+        c3_s4 yf[NT][2], xf[3][2];
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                xf[j][hf] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) c3_s4*)(xs + (frow + 4 * hf) * XP + j * 32 + fsub));
+#pragma unroll
+            for (int i = 0; i < NT; ++i)
+                yf[i][hf] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) c3_s4*)(ys + (frow + 4 * hf) * YP + i * 32 + fsub));
+        }
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            const bf16x8_t a = *reinterpret_cast<const bf16x8_t*>(&yf[i][0]);
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, *reinterpret_cast<const bf16x8_t*>(&xf[j][0]), acc[i][j], 0, 0, 0);
+            if (want_bias) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    bsum[i] = __builtin_amdgcn_fdot2_f32_bf16(bf16x2_t{a[2 * q], a[2 * q + 1]}, ones2, bsum[i], false);
+            }
+        }
+        __syncthreads();
+    }
+    // lane holds D[n = 16 i + 4 (lane >> 4) + r][k = 16 j + (lane & 15)] and, over its four lane groups, the column sum of n = 16 i + (lane & 15)
+    float* red = reinterpret_cast<float*>(smem);
+    for (int w = 0; w < 4; ++w) {
+        if (wv == w) {
+#pragma unroll
+            for (int i = 0; i < NT; ++i) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float* p = red + (16 * i + 4 * (lane >> 4) + r) * 48 + 16 * j + (lane & 15);
+                        *p = (w ? *p : 0.f) + acc[i][j][r];
+                    }
+                float v = bsum[i];
+                v += __shfl_xor(v, 16, 64);
+                v += __shfl_xor(v, 32, 64);
+                if (lane < 16) {
+                    float* p = red + N * 48 + 16 * i + lane;
+                    *p = (w ? *p : 0.f) + v;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    float* pp = part + (long)blockIdx.x * P::PART;
+    for (int i = tid; i < P::PART; i += 256) pp[i] = red[i];
+}
+
+// dW[n][k] (+)= alpha * sum_s part[s][n][k], dbias[n] += alpha * sum_s part[s][N * 48 + n]: 16 elements x 16 slices of the partials per
+// workgroup, the slices added in a fixed order
+__global__ __launch_bounds__(256) void stem4_wgrad_reduce(const float* __restrict__ part, int nparts, int N, float alpha, int add,
+                                                          float* __restrict__ dW, long ldw, float* __restrict__ dbias) {
+    __shared__ float sh[16][16];
+    const int total = N * 49, el = threadIdx.x & 15, sl = threadIdx.x >> 4;
+    const int e = blockIdx.x * 16 + el;
+    float a = 0.f;
+    if (e < total) {
+#pragma unroll 4
+        for (int s = sl; s < nparts; s += 16) a += part[(long)s * total + e];
+    }
+    sh[sl][el] = a;
+    __syncthreads();
+    if (sl == 0 && e < total) {
+        float v = 0.f;
+#pragma unroll
+        for (int s = 0; s < 16; ++s) v += sh[s][el];
+        v *= alpha;
+        if (e < N * 48) {
+            const int n = e / 48, k = e - n * 48;
+            float* p = dW + (long)n * ldw + k;
+            *p = add ? *p + v : v;
+        } else if (dbias) {
+            dbias[e - N * 48] += v;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int ga_stem4_ln_fwd(const float* x, const void* W, int64_t ldw, const float* bias, const float* gamma, const float* beta,
@@ -959,6 +1127,37 @@ size_t ga_conv3_c64_wgrad_workspace(const ga_wgrad_desc* d) {
     if (d->x_kind == GA_A_CONV3S2 && d->x_C == 8) return (size_t)conv0_wgrad_wgs(d) * 64 * 72 * sizeof(float);
     const int wgs = d->x_kind == GA_A_CONV3S2 ? conv3s2_wgrad_wgs(d) : conv3_wgrad_wgs(d);
     return (size_t)wgs * 64 * 576 * sizeof(float);
+}
+
+// ga_wgrad's GA_A_STEM4_NCHW product (bf16, N = 96 / 128, K = 48): workgroups of the direct form (0: does not apply)
+static int stem4_wgrad_wgs(const ga_wgrad_desc* d) {
+    if (!GA_KNOB("STEM4_WGRAD_DIRECT", 1)) return 0;
+    if (d->dtype != GA_BF16 || d->x_kind != GA_A_STEM4_NCHW || (d->N != 96 && d->N != 128) || d->K != 48 || d->x_C != 3 || d->batch != 1 ||
+        d->x_act != GA_ACT_NONE || d->ldy != d->N)
+        return 0;
+    if (d->x_H <= 0 || d->x_W <= 0 || d->x_H % 4 != 0 || d->x_W % 4 != 0) return 0;
+    const long ohw = (long)(d->x_H / 4) * (d->x_W / 4);
+    if ((long)d->M % ohw != 0 || (long)d->M * 48 >= (1L << 31)) return 0;
+    int cus = 256;
+    ga_device_info(&cus, nullptr, nullptr);
+    return (int)std::min<long>(((long)d->M + 127) / 128, 2L * cus);
+}
+size_t ga_stem4_wgrad_workspace(const ga_wgrad_desc* d) { return (size_t)stem4_wgrad_wgs(d) * d->N * 49 * sizeof(float); }
+
+int ga_stem4_wgrad_try(const ga_wgrad_desc* d, hipStream_t s) {
+    const int wgs = stem4_wgrad_wgs(d);
+    if (!wgs || !d->workspace || (size_t)d->ws_bytes < (size_t)wgs * d->N * 49 * sizeof(float)) return 0;
+    float* part = reinterpret_cast<float*>(d->workspace);
+    const int want_bias = d->dbias != nullptr;
+    if (d->N == 96)
+        hipLaunchKernelGGL(stem4_wgrad_kernel<6>, dim3(wgs), dim3(256), S4W<6>::LDS, s, (const bf16_t*)d->Y, (const float*)d->X, part, (int)d->M,
+                           d->x_H, d->x_W, want_bias);
+    else
+        hipLaunchKernelGGL(stem4_wgrad_kernel<8>, dim3(wgs), dim3(256), S4W<8>::LDS, s, (const bf16_t*)d->Y, (const float*)d->X, part, (int)d->M,
+                           d->x_H, d->x_W, want_bias);
+    hipLaunchKernelGGL(stem4_wgrad_reduce, dim3(cdiv(d->N * 49, 16)), dim3(256), 0, s, part, wgs, d->N, d->alpha,
+                       (int)(d->accumulate || d->split_m > 1), d->dW, (long)d->ldw, d->dbias);
+    return 1;
 }
 
 int ga_conv0_c8_wgrad_try(const ga_wgrad_desc* d, hipStream_t s) {

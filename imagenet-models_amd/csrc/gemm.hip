@@ -1780,9 +1780,15 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_tn_kernel(const ga_wgrad_des
 // kernel (the DMA writes LDS lane-linearly, so the swizzle is applied to the SOURCE chunk each lane fetches).
 // vs the 128 x 128 form: half the operand bytes per FLOP from L2 and no staging registers / ds_writes.
 // Column sums of Y (bias gradient) ride along as one extra MFMA per fragment against a constant ones operand.
+// P2: X is the GA_A_PATCH2 gather of an NHWC map (weight gradient of the 2 x 2 / stride-2 downsample convs).  Row m of the
+// operand is two runs of 2C contiguous elements one image row apart, and its patch origin is (2m + W (m / OW)) C (H, W even).
+// The run is chosen by the lane's COLUMN (a constant added to the lane offset for columns >= 2C; a 16-byte chunk never
+// straddles 2C when C % 8 == 0), the origin by the ROW: the lane offsets advance by 32 rows per stage with one carry into
+// the image row each -- no division and no gather code in the loop, the same four DMA operations per stage.
 // ================================================================================================
 constexpr int kTn2Threads = 512, kTn2Stage = 32768, kTn2Smem = 4 * kTn2Stage;
 
+template <bool P2>
 __global__ __launch_bounds__(kTn2Threads) void gemm_tn2_kernel(const ga_wgrad_desc d, const int split_m,
                                                                float* __restrict__ part) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1814,6 +1820,7 @@ __global__ __launch_bounds__(kTn2Threads) void gemm_tn2_kernel(const ga_wgrad_de
                               : reinterpret_cast<const bf16_t*>(d.X) + zx * d.strideX;
     const int lrow = 16 * (wave & 1) + (lane >> 4);                // + 4*i
     const int pc = lane & 15;
+    const bool xp2 = P2 && !is_y;                                  // this wave fetches patch rows
     // source chunk for i even / odd pairs: swizzle = ((row&3)<<1) | (((row>>3)&1)<<3), row&3 = (lane>>4)&3, row bit 3 = (i>>1)&1
     const int sw_lo = ((lane >> 4) & 3) << 1;
     long goff[2];
@@ -1821,20 +1828,51 @@ __global__ __launch_bounds__(kTn2Threads) void gemm_tn2_kernel(const ga_wgrad_de
     for (int b = 0; b < 2; ++b) {
         int c = col0 + ((pc ^ (sw_lo | (b << 3))) << 3);
         if (c >= ncols) c = 0;                                     // feeds output columns that are never written
-        goff[b] = (long)lrow * ld + c;
+        if (xp2) goff[b] = c + (c >= 2 * d.x_C ? (long)(d.x_W - 2) * d.x_C : 0);   // second run: one image row below the first
+        else goff[b] = (long)lrow * ld + c;
     }
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
-    // LDS-DMA through a buffer resource: 32-bit lane offsets (constant over the launch) + the stage's row offset as scalar
-    const u32x4_s rs = make_rsrc(gsrc, 0xffffffffu);
+    // LDS-DMA through a buffer resource: 32-bit lane offsets (constant over the launch) + the stage's row offset as scalar.
+    // The patch operand's window is the exact extent of its NHWC map (4 M C elements): a wrong offset reads zeros
+    const u32x4_s rs = make_rsrc(gsrc, xp2 ? (unsigned)(8L * d.M * d.x_C) : 0xffffffffu);
     unsigned voff[4];
+    // patch rows: the lane offset itself walks the rows (scalar offset 0).  ox = column of the row's output pixel; 32 rows
+    // further are p2_q output rows and p2_r pixels on, with a carry into one more output row = one more image row of W C
+    [[maybe_unused]] unsigned p2_ox[4];
+    [[maybe_unused]] unsigned p2_ow = 1, p2_r = 0, p2_step = 0, p2_carry = 0;
+    if (xp2) {
+        p2_ow = (unsigned)d.x_W >> 1;
+        const unsigned q = 32u / p2_ow, rowb = (unsigned)(d.x_W * d.x_C) * 2u;
+        p2_r = 32u - q * p2_ow;
+        p2_step = 128u * (unsigned)d.x_C + q * rowb;               // bytes: 2 * 32 pixels of C + q image rows
+        p2_carry = rowb;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) voff[i] = (unsigned)(goff[(i >> 1) & 1] + (long)(4 * i) * ld) * 2u;
-    auto stage_load = [&](int s, int buf) {
+        for (int i = 0; i < 4; ++i) {
+            const unsigned m = (unsigned)s_begin * 32u + (unsigned)(lrow + 4 * i), t = m / p2_ow;
+            p2_ox[i] = m - t * p2_ow;
+            voff[i] = (unsigned)(((long)(2u * m + (unsigned)d.x_W * t)) * d.x_C + goff[(i >> 1) & 1]) * 2u;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) voff[i] = (unsigned)(goff[(i >> 1) & 1] + (long)(4 * i) * ld) * 2u;
+    }
+    auto stage_load = [&](int s, int buf) __attribute__((always_inline)) {   // called for s_begin, s_begin + 1, ... in order
         if (!sub_live) return;
-        const unsigned soff = (unsigned)s * 64u * (unsigned)ld;                    // bytes of 32 rows
+        const unsigned soff = xp2 ? 0u : (unsigned)s * 64u * (unsigned)ld;         // bytes of 32 rows
         const unsigned dst = lds0 + buf * kTn2Stage + sub * 8192 + (wave & 1) * 4096;
 #pragma unroll
         for (int i = 0; i < 4; ++i) blds16(rs, voff[i], soff, dst + i * 1024);
+        if constexpr (P2) {
+            if (xp2) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    p2_ox[i] += p2_r;
+                    const bool carry = p2_ox[i] >= p2_ow;
+                    p2_ox[i] -= carry ? p2_ow : 0u;
+                    voff[i] += p2_step + (carry ? p2_carry : 0u);
+                }
+            }
+        }
     };
 
     // ---- MFMA role
@@ -1970,9 +2008,17 @@ __global__ __launch_bounds__(256) void tn2_reduce_kernel(const float* __restrict
 
 // the wide form needs whole 32-row stages, plain bf16 operands, and an output that is accumulated into (so that it
 // may choose its own row split); it pays once the reduction is long enough to amortise the 256 x 256 tile
+// GA_A_PATCH2 operands (TN2_PATCH2, default 1): NHWC map of even sides with C % 8 == 0, K == 4 C, byte offsets < 2^31
 bool tn2_eligible(const ga_wgrad_desc* d) {
-    return GA_KNOB("TN2", 1) && d->dtype == GA_BF16 && d->x_kind == GA_A_PLAIN && d->x_act == GA_ACT_NONE && d->M % 32 == 0 &&
-           d->M >= 8192 && (d->accumulate || d->split_m > 1) && (long)d->M * d->ldy < (1L << 31) && (long)d->M * d->ldx < (1L << 31);   // 32-bit byte offsets
+    if (!(GA_KNOB("TN2", 1) && d->dtype == GA_BF16 && d->x_act == GA_ACT_NONE && d->M % 32 == 0 && d->M >= 8192 &&
+          (d->accumulate || d->split_m > 1) && (long)d->M * d->ldy < (1L << 31)))                    // 32-bit byte offsets
+        return false;
+    if (d->x_kind == GA_A_PLAIN) return (long)d->M * d->ldx < (1L << 31);
+    if (d->x_kind == GA_A_PATCH2)
+        return GA_KNOB("TN2_PATCH2", 1) && d->x_C > 0 && d->x_C % 8 == 0 && d->K == 4 * d->x_C && d->x_H > 0 && d->x_W > 0 &&
+               d->x_H % 2 == 0 && d->x_W % 2 == 0 && d->M % ((long)(d->x_H / 2) * (d->x_W / 2)) == 0 &&
+               8L * d->M * d->x_C < (1L << 31);
+    return false;
 }
 
 // row split of the wide form and the bytes of partial-tile workspace it wants (0: combine with atomics)
@@ -2379,8 +2425,12 @@ extern "C" int ga_wgrad(const ga_wgrad_desc* d, ga_stream_t stream) {
     if (d->x_kind == GA_A_CONV3 && ga_conv3_c64_wgrad_try(d, s)) return ga_check_launch("ga_wgrad");   // 64 -> 64 channels: direct form
     if (d->x_kind == GA_A_CONV3S2 && d->x_C == 64 && ga_conv3s2_c64_wgrad_try(d, s)) return ga_check_launch("ga_wgrad");   // ... stride 2
     if (d->x_kind == GA_A_CONV3S2 && d->x_C == 8 && ga_conv0_c8_wgrad_try(d, s)) return ga_check_launch("ga_wgrad");        // 3 (8) -> 64, stride 2
+    if (d->x_kind == GA_A_STEM4_NCHW && ga_stem4_wgrad_try(d, s)) return ga_check_launch("ga_wgrad");                       // ConvNeXt stem
     if (tn2_eligible(d)) {
-        static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn2_kernel),
+        const bool p2 = d->x_kind == GA_A_PATCH2;
+        static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn2_kernel<false>),
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, kTn2Smem) == hipSuccess &&
+                                    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn2_kernel<true>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, kTn2Smem) == hipSuccess;
         GA_REQUIRE(attr_ok, "ga_wgrad: cannot reserve %d bytes of LDS", kTn2Smem);
         int split;
@@ -2391,7 +2441,8 @@ extern "C" int ga_wgrad(const ga_wgrad_desc* d, ga_stream_t stream) {
         float* part = (need && d->workspace && (size_t)d->ws_bytes >= need) ? reinterpret_cast<float*>(d->workspace) : nullptr;
         GA_REQUIRE(!part || aligned16(part), "ga_wgrad: workspace must be 16-byte aligned");
         const long nk = (long)d->N * d->K;
-        hipLaunchKernelGGL(gemm_tn2_kernel, grid2, block2, kTn2Smem, s, *d, split, part);
+        if (p2) hipLaunchKernelGGL(gemm_tn2_kernel<true>, grid2, block2, kTn2Smem, s, *d, split, part);
+        else hipLaunchKernelGGL(gemm_tn2_kernel<false>, grid2, block2, kTn2Smem, s, *d, split, part);
         if (part)
             hipLaunchKernelGGL(tn2_reduce_kernel, dim3((unsigned)std::min<long>(2048, cdiv(nk, 1024)), d->batch), dim3(256),
                                0, s, part, split, nk, d->K, d->alpha, d->dW, d->ldw, d->strideW);
@@ -2408,6 +2459,7 @@ extern "C" int ga_wgrad(const ga_wgrad_desc* d, ga_stream_t stream) {
 extern "C" size_t ga_wgrad_workspace(const ga_wgrad_desc* d) {
     if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch < 1) return 0;
     if (d->x_kind == GA_A_CONV3 || (d->x_kind == GA_A_CONV3S2 && (d->x_C == 64 || d->x_C == 8))) return ga_conv3_c64_wgrad_workspace(d);
+    if (d->x_kind == GA_A_STEM4_NCHW) return ga_stem4_wgrad_workspace(d);
     if (!tn2_eligible(d)) return 0;
     int split;
     return tn2_plan(d, &split);
