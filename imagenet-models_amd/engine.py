@@ -1434,14 +1434,17 @@ class GAEngine:
     U8_MEAN = (0.485 * 255, 0.456 * 255, 0.406 * 255)
     U8_STD = (0.229 * 255, 0.224 * 255, 0.225 * 255)
 
+    def input_stats(self):
+        """(mean, std) of the uint8 normalisation, 0..255 units: the model's input_mean / input_std or the ImageNet ones"""
+        return getattr(self.m, 'input_mean', None) or self.U8_MEAN, getattr(self.m, 'input_std', None) or self.U8_STD
+
     def _normalize_u8(self, x):
         """a uint8 (B, 3, H, W) batch is normalised on the device into an engine-owned fp32 buffer (no host round trip)"""
         if x.dtype != torch.uint8:
             return x
         assert x.is_cuda and tuple(x.shape) == (self.B, 3, self.img, self.img), f'uint8 input of shape {tuple(x.shape)}'
         out = self.buf('x.u8norm', (self.B, 3, self.img, self.img), torch.float32)
-        mean = getattr(self.m, 'input_mean', None) or self.U8_MEAN
-        std = getattr(self.m, 'input_std', None) or self.U8_STD
+        mean, std = self.input_stats()
         Plan(eager=True).u8_normalize(x.contiguous(), out, mean, std)
         return out
 

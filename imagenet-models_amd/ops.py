@@ -820,6 +820,17 @@ class Plan:
         s = (C.c_float * CH)(*[float(v) for v in std])
         self._add('ga_u8_normalize', (_ptr(x), _ptr(out), B, CH, H, W, m, s), label, keep=(x, out, m, s))
 
+    def input_erase(self, x, out, boxes, max_count, mode, seed, offset, mean=None, std=None, label=None):
+        """RandomErasing fused with the uint8 normalisation (or a copy of an fp32 x): boxes = device int32 (B, max_count, 4) of
+        top, left, h, w; mode 0 const / 1 rand / 2 pixel; mean / std (0..255 units) are used for uint8 x only"""
+        B, CH, H, W = x.shape
+        u8 = x.dtype == torch.uint8
+        m = (C.c_float * CH)(*[float(v) for v in mean]) if u8 else None
+        s = (C.c_float * CH)(*[float(v) for v in std]) if u8 else None
+        mask = (1 << 64) - 1
+        self._add('ga_input_erase', (_ptr(x), int(u8), _ptr(out), B, CH, H, W, m, s, _ptr(boxes), int(max_count), int(mode),
+                                     int(seed) & mask, int(offset) & mask), label, keep=(x, out, boxes, m, s))
+
     def mixup_batch(self, x, out, lam, cutmix=False, box=(0, 0, 0, 0), label=None):
         B, CH, H, W = x.shape
         yl, yh, xl, xh = (int(v) for v in box)

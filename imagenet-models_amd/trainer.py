@@ -66,8 +66,11 @@ class TrainStep:
     def __init__(self, model, optimizer, batch, lam=0.0, loss='ce', smoothing=0.0, grad_accumulation=1,
                  process_group=None, clip_grad=None, clip_mode='norm', broadcast_buffers=True, bucket_elems=BUCKET_ELEMS,
                  mixup_fn=None, bce_target_thresh=None, comm=None, force_buckets=False, nan_guard=False,
-                 overlap_optimizer=False):
-        """comm: an imagenet_models_amd.NativeComm -- the gradient buckets (and the BatchNorm-buffer broadcast) go through the
+                 overlap_optimizer=False, random_erasing=None):
+        """random_erasing: an imagenet_models_amd.RandomErasing -- the input goes normalise -> erase -> mixup -> engine, the order
+        of the reference (timm's PrefetchLoader erases the normalised batch on the device, mixup_fn follows: MAP/train.py:643-646);
+        for a uint8 batch the erase pass IS the normalisation (ga_input_erase), so the batch is passed over once.
+        comm: an imagenet_models_amd.NativeComm -- the gradient buckets (and the BatchNorm-buffer broadcast) go through the
         library's own RCCL entry points (ga_allreduce_bucket on a side stream) instead of torch.distributed.
         force_buckets: take the segmented-backward + bucketed-reduction path even with one rank (tests: the real collective
         path on a one-GPU box).
@@ -80,6 +83,7 @@ class TrainStep:
         # mixup / cutmix (imagenet_models_amd.Mixup, GA/train.py:727-728): applied to every batch, the loss then runs on the
         # dense target it returns (SoftTargetCrossEntropy / BinaryCrossEntropy, train.py:616-621)
         self.mixup_fn = mixup_fn
+        self.random_erasing = random_erasing
         self.bce_threshold = -1.0 if bce_target_thresh is None else float(bce_target_thresh)
         self.accum = grad_accumulation
         self.pg = process_group
@@ -182,6 +186,8 @@ class TrainStep:
                 dist.broadcast(self.flat_buffers, 0, group=self.pg)
         # the reference divides the loss by grad_accumulation (train.py:750); DDP averages over ranks
         scale = 1.0 / (self.accum * self.world)
+        if self.random_erasing is not None:
+            x = self.random_erasing(x, *eng.input_stats())
         if self.mixup_fn is not None:
             # a uint8 batch (PrefetchLoader layout) is normalised on the device FIRST: Mixup blends normalised pixels, and a
             # float tensor coming back from it would make the engine skip the normalisation

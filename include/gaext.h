@@ -535,6 +535,20 @@ int ga_mixup_target(const int64_t* target, float* out, int B, int NC, double lam
 /* uint8 NCHW batch (timm fast_collate) -> fp32 NCHW, out = (x - mean[c]) / std[c]; mean / std are HOST arrays of CH <= 4 floats
  * (already scaled by 255 as timm's PrefetchLoader holds them, GA/train.py:567-595); H*W a multiple of 4 */
 int ga_u8_normalize(const void* x, float* out, int B, int CH, int H, int W, const float* mean, const float* std, ga_stream_t stream);
+/* timm RandomErasing as PrefetchLoader runs it: on the device, on the normalised batch, ahead of mixup (MAP/train.py:214-220,
+ * 643-646).  One out-of-place pass: out = ga_u8_normalize(x) (x_is_u8; same arithmetic, bit-identical) or a copy of the fp32 x,
+ * except inside the boxes of a sample, where it is the fill.  boxes: DEVICE int32 [B][max_count][4] = top, left, h, w, drawn by the
+ * host (imagenet_models_amd.RandomErasing); h == 0: unused slot; where boxes of a sample overlap the later one wins.
+ * mode 0 'const': zeros; 1 'rand': one N(0,1) colour per (box, channel); 2 'pixel': N(0,1) per element.  H*W % 4 == 0.
+ * The normals are a pure function of (seed, offset, index) -- no state, no atomics, independent of the launch shape:
+ *   Philox4x32-10, key = (seed[31:0], seed[63:32]), counter = (q[31:0], q[63:32], offset[31:0], offset[62:32] | stream << 31);
+ *   pixel (stream 0): q = i >> 2 for the flat element index i = ((b*CH + c)*H + y)*W + x, element i takes normal n[i & 3];
+ *   rand (stream 1): q = (b*max_count + j)*CH + c for box j, the colour is n[0];
+ *   uniforms u_k = ((r_k >> 9) + 0.5) * 2^-23 of the outputs r0..r3 (never 0: no log(0));
+ *   n0 = R(u0) cos(2 pi u1), n1 = R(u0) sin(2 pi u1), n2 = R(u2) cos(2 pi u3), n3 = R(u2) sin(2 pi u3), R(u) = sqrt(-2 ln u).
+ * A caller advances `offset` (< 2^63) by one per step for fresh noise from one seed. */
+int ga_input_erase(const void* x, int x_is_u8, float* out, int B, int CH, int H, int W, const float* mean, const float* std,
+                   const int32_t* boxes, int max_count, int mode, uint64_t seed, uint64_t offset, ga_stream_t stream);
 /* adaptive gradient clipping (timm adaptive_clip_grad, clip_mode 'agc'): units = int64 {offset, length} pairs into the flat fp32
  * parameter / gradient buffers (a row of a >= 2-d parameter or a whole <= 1-d one); per unit
  * g *= max(|p|, eps) * clip_factor / max(|g|, 1e-6) where |g| exceeds max(|p|, eps) * clip_factor */

@@ -52,6 +52,12 @@ parser.add_argument('--mixup-prob', type=float, default=1.0)
 parser.add_argument('--mixup-switch-prob', type=float, default=0.5)
 parser.add_argument('--mixup-mode', default='batch', help='only "batch" is built')
 parser.add_argument('--mixup-off-epoch', type=int, default=0)
+# RandomErasing on the device (MAP/train.py:214-221; every MAP recipe runs --remode pixel --reprob 0.25)
+parser.add_argument('--reprob', type=float, default=0., metavar='PCT', help='Random erase prob (default: 0.)')
+parser.add_argument('--remode', type=str, default='pixel', help='Random erase mode (default: "pixel")')
+parser.add_argument('--recount', type=int, default=1, help='Random erase count (default: 1)')
+parser.add_argument('--resplit', action='store_true', default=False, help='Do not random erase first (clean) augmentation split '
+                    '(inert here: the reference splits only under --aug-splits, which is not built)')
 parser.add_argument('--drop-path', type=float, default=None)
 parser.add_argument('--grad-accumulation', type=int, default=1)
 parser.add_argument('--GA_lam', type=float, default=0)
@@ -177,10 +183,12 @@ def main():
             dist.init_process_group('nccl', init_method='env://', device_id=torch.device('cuda', local))
         else:
             dist.init_process_group(backend, init_method='env://')
+    import random
     import numpy as np
     import imagenet_models_amd as A
     torch.manual_seed(args.seed + rank)
     np.random.seed(args.seed + rank)          # timm random_seed(): mixup draws lam / boxes from numpy's global generator
+    random.seed(args.seed + rank)             # ... and RandomErasing draws its boxes from Python's
     model = A.create_model(args.model, pretrained=False, num_classes=args.num_classes, drop_path_rate=args.drop_path,
                            math_mode='fp32' if args.fp32 else 'bf16').cuda()
     if world > 1:
@@ -207,10 +215,15 @@ def main():
         mixup_fn = A.Mixup(mixup_alpha=args.mixup, cutmix_alpha=args.cutmix, cutmix_minmax=args.cutmix_minmax, prob=args.mixup_prob,
                            switch_prob=args.mixup_switch_prob, mode=args.mixup_mode, label_smoothing=args.smoothing,
                            num_classes=model.num_classes)
+    # RandomErasing as timm's create_loader builds it (re_prob / re_mode / re_count: the MAX count; num_splits 0 without aug-splits)
+    random_erasing = None
+    if args.reprob > 0.:
+        random_erasing = A.RandomErasing(probability=args.reprob, mode=args.remode, max_count=args.recount, num_splits=0,
+                                         seed=args.seed + rank)
     step_fn = A.TrainStep(model, opt, args.batch_size, lam=lam, loss='bce' if args.bce_loss else 'ce',
                           smoothing=args.smoothing, grad_accumulation=args.grad_accumulation,
                           clip_grad=args.clip_grad, clip_mode=args.clip_mode, broadcast_buffers=not args.no_ddp_bb,
-                          mixup_fn=mixup_fn, bce_target_thresh=args.bce_target_thresh, comm=comm)
+                          mixup_fn=mixup_fn, bce_target_thresh=args.bce_target_thresh, comm=comm, random_erasing=random_erasing)
     model_ema = A.ModelEma(model, args.model_ema_decay) if args.model_ema else None
     img = getattr(model, 'cfg', {}).get('img_size', 224)
     loader = SyntheticLoader(args.batch_size, args.steps_per_epoch, model.num_classes, args.seed + rank, 'cuda', img)
