@@ -155,6 +155,10 @@ _SIGS = {
     'ga_chan_scale': ([vp, vp, vp, vp, i32, i32, i32, i32, vp], i32),
     'ga_gram_pack_fwd': ([vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
     'ga_gram_pack_bwd': ([vp, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
+    'ga_gram_f64_fwd_workspace': ([i32, i32], C.c_size_t),
+    'ga_gram_f64_bwd_workspace': ([i32, i32], C.c_size_t),
+    'ga_gram_f64_fwd': ([vp, vp, vp, vp, C.c_size_t, i32, i32, i32, i32, i32, i32, i32, vp], i32),
+    'ga_gram_f64_bwd': ([vp, vp, vp, vp, vp, vp, C.c_size_t, i32, i32, i32, i32, i32, i32, i32, vp], i32),
     'ga_token_cat': ([vp, vp, vp, i32, i32, i32, i32, vp], i32),
     'ga_token_split': ([vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
     'ga_class_attn_fwd': ([vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp], i32),

@@ -5,7 +5,7 @@ import torch.nn as nn
 
 from .flat_model import FlatModel
 from .map_convnext import _Block, _LN, _init_weights
-from .registry import register_model
+from .registry import register_model, reject_gram_fp64
 
 __all__ = ['ConvNeXt']
 
@@ -47,6 +47,7 @@ class ConvNeXt(FlatModel):
 
 
 def _create(variant, pretrained=False, **kwargs):
+    reject_gram_fp64(variant, kwargs)
     kwargs.pop('pretrained_cfg', None)
     kwargs.pop('pretrained_cfg_overlay', None)
     kwargs.pop('in_22k', None)

@@ -1004,6 +1004,11 @@ class GAEngine:
         #  on the alignment-free ga_small_linear kernels)
         return E % nh == 0 and E % 8 == 0 and g % 8 == 0 and cout % 8 == 0 and cout % groups == 0 and cout % mg == 0
 
+    def _gram_fp64(self):
+        """get_gram's float64 branch (ga_convnext.py:456-457: `self.training and B < 128`, B the per-step micro-batch), taken only
+        by a model built with gram_fp64=True"""
+        return bool(self.cfg.get('gram_fp64')) and self.training and self.B < 128
+
     def _head_fwd(self, k, x4, M4, cout, Hc):
         cfg = self.cfg
         if not self._head_supported():
@@ -1057,19 +1062,29 @@ class GAEngine:
         if self.shared_tok:       # padded head width (== the real one for the *_768 / *_1024 variants)
             E, hd = self.Ea, self.hd_p
         g1 = h['g1']
-        # --- Gram vector (fp32 accumulate; the reference's fp64 branch for train & B<128 is covered by the 1e-3 gate)
-        alpha = 1.0 / (Hc * Hc * HW)
-        h['alpha'] = alpha
-        G = self.tmp('gramG', (B, g, g), torch.float32)
-        F.wgrad(g1, g1, G, HW, g, g, dt, batch=B, strideY=HW * g, strideX=HW * g, strideW=g * g, split_m=1,
-                accumulate=False, alpha=alpha, label=f'gram.{k}')
         ntri = g * (g + 1) // 2
         Kg = ntri // groups
         Kp = pad8(Kg)
         h['Kg'], h['Kp'] = Kg, Kp
         h['vec'] = self.act(f'gram.{k}.vec', (B, groups * Kp))
-        h['inv'] = self.act(f'gram.{k}.inv', (B,), torch.float32)
-        F.gram_pack_fwd(G, h['vec'], h['inv'], B, g, groups, Kp, dt, label=f'gram.{k}.pack')
+        h['gram64'] = self._gram_fp64()
+        if h['gram64']:
+            # --- Gram vector through get_gram's float64 branch (opt-in, gram_fp64=True): x / H in the activation dtype, everything
+            # up to the normalised vector in double, one rounding on the way out; the packed double Gram entries and 1 / norm stay
+            # for the backward
+            h['Hc'] = Hc
+            h['G64'] = self.act(f'gram.{k}.G64', (B, ntri), torch.float64)
+            h['inv'] = self.act(f'gram.{k}.inv64', (B,), torch.float64)
+            F.gram_f64_fwd(g1, h['vec'], h['inv'], h['G64'], B, HW, g, Hc, groups, Kp, dt, label=f'gram.{k}.f64')
+        else:
+            # --- Gram vector (fp32 accumulate; the reference's fp64 branch for train & B<128 is covered by the 1e-3 gate)
+            alpha = 1.0 / (Hc * Hc * HW)
+            h['alpha'] = alpha
+            G = self.tmp('gramG', (B, g, g), torch.float32)
+            F.wgrad(g1, g1, G, HW, g, g, dt, batch=B, strideY=HW * g, strideX=HW * g, strideW=g * g, split_m=1,
+                    accumulate=False, alpha=alpha, label=f'gram.{k}')
+            h['inv'] = self.act(f'gram.{k}.inv', (B,), torch.float32)
+            F.gram_pack_fwd(G, h['vec'], h['inv'], B, g, groups, Kp, dt, label=f'gram.{k}.pack')
         # --- gram_embedding: grouped 1x1 + BN on (B, cout)
         pre = f'gram_embedding.{k}.'
         cg = cout // groups
@@ -1263,11 +1278,15 @@ class GAEngine:
                      strideW=cg * Kg, dbias=self.grad(pre + '0.bias'), strideDbias=cg, label=pre + 'wg')
             Bk.gemm(de, W[pre + '0.weight.T'], dvec, B, Kg, cg, dt, lda=cout, batch=groups, strideA=cg, strideB=Kg * pad8(cg),
                     ldb=pad8(cg), ldc=groups * Kp, strideC=Kp, label=pre + 'dg')
-        S = self.tmp('gramS', (B, g, g))
-        Bk.gram_pack_bwd(dvec, h['vec'], h['inv'], S, B, g, groups, Kp, dt, label=f'gram.{k}.packb')
         dg1 = self.tmp('dg1', (M4, g))
-        Bk.gemm(h['g1'], S, dg1, HW, g, g, dt, batch=B, strideA=HW * g, strideB=g * g, strideC=HW * g, alpha=h['alpha'],
-                label=f'gram.{k}.dx')
+        if h['gram64']:
+            S64 = self.tmp('gramS64', (B, g, g), torch.float64)
+            Bk.gram_f64_bwd(dvec, h['g1'], h['G64'], h['inv'], dg1, S64, B, HW, g, h['Hc'], groups, Kp, dt, label=f'gram.{k}.f64b')
+        else:
+            S = self.tmp('gramS', (B, g, g))
+            Bk.gram_pack_bwd(dvec, h['vec'], h['inv'], S, B, g, groups, Kp, dt, label=f'gram.{k}.packb')
+            Bk.gemm(h['g1'], S, dg1, HW, g, g, dt, batch=B, strideA=HW * g, strideB=g * g, strideC=HW * g, alpha=h['alpha'],
+                    label=f'gram.{k}.dx')
         dg0 = self.tmp('dg0', (M4, g))
         self._gram_layer_bwd(h, dg1, dg0)
         self._head_contract_bwd(h, k, dg0, M4)

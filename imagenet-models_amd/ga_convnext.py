@@ -98,7 +98,7 @@ class GA_ConvNeXt(FlatModel):
                  depths=(3, 3, 9, 3, 1), dims=(96, 192, 384, 768, 768), ls_init_value=1e-6, conv_mlp=False,
                  head_init_scale=1., norm_layer=None, drop_rate=0., drop_path_rate=0.,
                  branches=5, gram_embedding_gropus=8, dim_embed=128, stage3_naggre=2, gram_dim=192, gram_layer=True,
-                 math_mode=None):
+                 math_mode=None, gram_fp64=False):
         super().__init__()
         assert output_stride == 32 and patch_size == 4 and in_chans == 3 and len(dims) == 5
         assert not conv_mlp and norm_layer is None and gram_layer, 'only the configuration the reference registers'
@@ -108,7 +108,10 @@ class GA_ConvNeXt(FlatModel):
         self.cfg = dict(depths=tuple(depths), dims=tuple(dims), branches=branches, gram_groups=gram_embedding_gropus,
                         dim_embed=dim_embed, naggre=stage3_naggre, gram_dim=gram_dim, num_heads=8, mlp_groups=4,
                         num_classes=num_classes, patch_size=patch_size, in_chans=in_chans,
-                        drop_path_rate=drop_path_rate)
+                        drop_path_rate=drop_path_rate,
+                        # get_gram's float64 branch for `training and B < 128` (ga_convnext.py:456-457) on the fp64 kernels; off: the
+                        # fp32-accumulate Gram path every committed bench and parity number was taken on
+                        gram_fp64=bool(gram_fp64))
         d = dims
         self.stem = nn.Sequential(nn.Conv2d(in_chans, d[0], kernel_size=patch_size, stride=patch_size),
                                   nn.LayerNorm(d[0], eps=1e-6))

@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from .flat_model import FlatModel, Holder
 from .ga_convnext import BottleneckParams, ClassAttnParams
-from .registry import register_model
+from .registry import register_model, reject_gram_fp64
 
 __all__ = ['GA_CSWinTransformer']
 
@@ -156,6 +156,7 @@ class GA_CSWinTransformer(FlatModel):
 
 
 def _create(variant, pretrained=False, **kwargs):
+    reject_gram_fp64(variant, kwargs)
     for k in ('pretrained_cfg', 'pretrained_cfg_overlay', 'features_only', 'default_cfg'):
         kwargs.pop(k, None)
     if pretrained:

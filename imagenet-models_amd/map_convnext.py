@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from .flat_model import FlatModel, Holder
-from .registry import register_model
+from .registry import register_model, reject_gram_fp64
 
 __all__ = ['MAP_ConvNeXt']
 
@@ -200,6 +200,7 @@ class MAP_ConvNeXt(FlatModel):
 
 
 def _create(variant, pretrained=False, **kwargs):
+    reject_gram_fp64(variant, kwargs)
     kwargs.pop('pretrained_cfg', None)
     kwargs.pop('pretrained_cfg_overlay', None)
     kwargs.pop('in_22k', None)

@@ -11,7 +11,7 @@ import torch.nn as nn
 from .flat_model import FlatModel, Holder
 from .map_convnext import _MAPHead
 from .map_vit import _VitBlock
-from .registry import register_model
+from .registry import register_model, reject_gram_fp64
 
 __all__ = ['MAP_PiT']
 
@@ -87,6 +87,7 @@ class MAP_PiT(FlatModel):
 
 @register_model
 def map_pit_s(pretrained=False, **kwargs):
+    reject_gram_fp64('map_pit_s', kwargs)
     kwargs.pop('pretrained_cfg', None)
     kwargs.pop('pretrained_cfg_overlay', None)
     if pretrained:

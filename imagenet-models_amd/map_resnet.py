@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from .flat_model import FlatModel
 from .map_convnext import _MAPHead
-from .registry import register_repaired_model
+from .registry import register_repaired_model, reject_gram_fp64
 
 __all__ = ['MAP_ResNet']
 
@@ -113,6 +113,7 @@ class MAP_ResNet(FlatModel):
 def map_resnet50(pretrained=False, **kwargs):
     """map_resnet.py:318-333 (pretrained=True there downloads a checkpoint: here it raises).  Repaired tier: the reference's forward
     fails for this name; the engine runs the MAP head on [stem, layer1..4]"""
+    reject_gram_fp64('map_resnet50', kwargs)
     for k in ('pretrained_cfg', 'pretrained_cfg_overlay', 'in_22k', 'drop_rate', 'drop_block_rate', 'global_pool', 'bn_momentum', 'bn_eps'):
         kwargs.pop(k, None)
     if pretrained:

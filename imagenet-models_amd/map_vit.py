@@ -8,7 +8,7 @@ import torch.nn as nn
 
 from .flat_model import FlatModel, Holder
 from .map_convnext import _MAPHead, _init_weights
-from .registry import register_model
+from .registry import register_model, reject_gram_fp64
 
 __all__ = ['MAP_ViT']
 
@@ -92,6 +92,7 @@ class MAP_ViT(FlatModel):
 
 
 def _create(variant, pretrained=False, **kwargs):
+    reject_gram_fp64(variant, kwargs)
     kwargs.pop('pretrained_cfg', None)
     kwargs.pop('pretrained_cfg_overlay', None)
     if pretrained:

@@ -16,7 +16,7 @@ import torch.nn as nn
 
 from .flat_model import FlatModel, Holder
 from .map_convnext import _MAPHead
-from .registry import register_extra_model
+from .registry import register_extra_model, reject_gram_fp64
 
 __all__ = ['MobileNetV1']
 
@@ -87,6 +87,7 @@ class MobileNetV1(FlatModel):
 
 
 def _create(variant, pretrained, use_map, num_classes=1000, **kwargs):
+    reject_gram_fp64(variant, kwargs)
     for k in ('pretrained_cfg', 'pretrained_cfg_overlay', 'in_22k', 'drop_rate'):
         kwargs.pop(k, None)
     if pretrained:

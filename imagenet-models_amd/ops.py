@@ -685,6 +685,21 @@ class Plan:
         self._add('ga_gram_pack_bwd', (_ptr(dvec), _ptr(vhat), _ptr(inv_norm), _ptr(S), B, Cdim, groups, Kp, dtype), label,
                   keep=(dvec, vhat, inv_norm, S))
 
+    @staticmethod
+    def _nbytes(t):
+        return 0 if t is None else t.numel() * t.element_size()
+
+    def gram_f64_fwd(self, x, vec, inv_norm, G64, B, HW, Cdim, H, groups, Kp, dtype, label=None):
+        """get_gram's float64 branch: vec from the gram layer's output x; G64 (float64, >= B * ntri) and inv_norm (float64 [B])
+        are kept for gram_f64_bwd"""
+        self._add('ga_gram_f64_fwd', (_ptr(x), _ptr(vec), _ptr(inv_norm), _ptr(G64), self._nbytes(G64), B, HW, Cdim, H, groups, Kp,
+                                      dtype), label, keep=(x, vec, inv_norm, G64))
+
+    def gram_f64_bwd(self, dvec, x, G64, inv_norm, dx, ws, B, HW, Cdim, H, groups, Kp, dtype, label=None):
+        """ws: float64 scratch of >= B * C * C entries (ga_gram_f64_bwd_workspace bytes)"""
+        self._add('ga_gram_f64_bwd', (_ptr(dvec), _ptr(x), _ptr(G64), _ptr(inv_norm), _ptr(dx), _ptr(ws), self._nbytes(ws), B, HW,
+                                      Cdim, H, groups, Kp, dtype), label, keep=(dvec, x, G64, inv_norm, dx, ws))
+
     def token_cat(self, cls, tok, u, B, N, Cdim, dtype, label=None):
         self._add('ga_token_cat', (_ptr(cls), _ptr(tok), _ptr(u), B, N, Cdim, dtype), label, keep=(cls, tok, u))
 

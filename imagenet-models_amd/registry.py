@@ -79,6 +79,14 @@ def model_entrypoint(name):
     return _entrypoints[name]
 
 
+def reject_gram_fp64(variant, kwargs):
+    """gram_fp64 is GA_ConvNeXt.get_gram's float64 branch (ga_convnext.py:456-457).  ga_cswin.get_gram and MAP's GramToken have no
+    such branch in the reference, so every other family refuses the kwarg instead of swallowing it."""
+    if 'gram_fp64' in kwargs:
+        raise ValueError(f'{variant}: gram_fp64 is only defined for the GA-ConvNeXt family (the float64 branch of '
+                         f'GA_ConvNeXt.get_gram); the reference has no such branch for this model')
+
+
 def create_model(model_name, pretrained=False, checkpoint_path='', scriptable=None, **kwargs):
     """timm.create_model semantics: kwargs whose value is None are dropped before reaching the factory."""
     if not is_model(model_name):

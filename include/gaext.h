@@ -363,6 +363,24 @@ int ga_gram_pack_fwd(const float* G, void* out, float* inv_norm, int B, int C, i
 int ga_gram_pack_bwd(const void* dvec, const void* vhat, const float* inv_norm, void* S, int B, int C, int groups,
                      int Kp, int dtype, ga_stream_t stream);
 
+/* The same Gram vector through get_gram's float64 branch (`self.training and B < 128`, ga_convnext.py:456-457), straight from
+ * the gram layer's NHWC output x[B][HW][C] (fp32 / bf16 per dtype) -- no ga_wgrad in front, no GEMM behind:
+ *   fwd: xh = x / H rounded to the input dtype, then widened; G = xh^T xh / HW, the i <= j gather and F.normalize (eps 1e-12)
+ *        in double; vec[B][groups][Kp] = the normalised vector rounded ONCE to dtype (pad columns zero).  Kept for the
+ *        backward: G64[B][C (C + 1) / 2] doubles (the raw packed entries, ga_gram_f64_fwd_workspace(B, C) bytes) and
+ *        inv_norm[B] doubles (1 / max(norm, 1e-12)).
+ *   bwd: dvec[B][groups][Kp] widened; d_raw = (dvec - vh <vh, dvec>) / norm with vh = G64 / norm in double; the symmetric S
+ *        (diagonal doubled) in `workspace` (ga_gram_f64_bwd_workspace(B, C) bytes, [B][C][C] doubles);
+ *        dxh = xh . S / HW in double, cast to dtype as torch casts the float64 gradient back (bf16: through fp32), then
+ *        dx[B][HW][C] = dxh / H in dtype.
+ * Fixed summation order, no atomics: two runs are bit-identical.  C % 8 == 0 and C (C + 1) / 2 % groups == 0 are required. */
+size_t ga_gram_f64_fwd_workspace(int B, int C);
+size_t ga_gram_f64_bwd_workspace(int B, int C);
+int ga_gram_f64_fwd(const void* x, void* vec, double* inv_norm, double* G64, size_t g64_bytes, int B, int HW, int C, int H,
+                    int groups, int Kp, int dtype, ga_stream_t stream);
+int ga_gram_f64_bwd(const void* dvec, const void* x, const double* G64, const double* inv_norm, void* dx, void* workspace,
+                    size_t ws_bytes, int B, int HW, int C, int H, int groups, int Kp, int dtype, ga_stream_t stream);
+
 /* Class attention with ONE query token (ClassAttn / LayerScaleBlockClassAttn, ga_convnext.py:153-187,244-248):
  *   token_cat: u[B][N+1][C] = cat(cls[B][C], tok[B][N][C]);  token_split: dcls (+)= du[:,0], dtok (+)= du[:,1:]
  *   class_attn: q [B][E], kv [B*(N)][2E] (k | v), E = heads*hd <= 64 per head; P fp32 [B][heads][N] saved. */

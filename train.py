@@ -77,6 +77,8 @@ parser.add_argument('--clip-grad', type=float, default=None, help='clip gradient
 parser.add_argument('--clip-mode', default='norm', help='"norm", "value" or "agc"')
 parser.add_argument('--amp', action='store_true', help='bf16 math mode (default)')
 parser.add_argument('--fp32', action='store_true', help='fp32 parity math mode')
+parser.add_argument('--gram-fp64', action='store_true', help='GA-ConvNeXt only: get_gram in float64 while training with a per-step '
+                    'batch below 128, as the reference does (ga_convnext.py:456-457); off by default')
 parser.add_argument('--channels-last', action='store_true', help='accepted for CLI compatibility (activations are always NHWC)')
 parser.add_argument('--synthetic', action='store_true')
 parser.add_argument('--device', default='cuda')
@@ -190,7 +192,7 @@ def main():
     np.random.seed(args.seed + rank)          # timm random_seed(): mixup draws lam / boxes from numpy's global generator
     random.seed(args.seed + rank)             # ... and RandomErasing draws its boxes from Python's
     model = A.create_model(args.model, pretrained=False, num_classes=args.num_classes, drop_path_rate=args.drop_path,
-                           math_mode='fp32' if args.fp32 else 'bf16').cuda()
+                           math_mode='fp32' if args.fp32 else 'bf16', gram_fp64=True if args.gram_fp64 else None).cuda()
     if world > 1:
         dist.broadcast(model.flat_state()['params'], 0)
         dist.broadcast(model.flat_state()['buffers'], 0)
