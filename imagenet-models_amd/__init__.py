@@ -22,6 +22,8 @@ from . import map_pit  # noqa: E402,F401  (registers map_pit_s)
 from . import convnext  # noqa: E402,F401  (registers the plain convnext_tiny / convnext_small of map_convnext.py)
 from .convnext import ConvNeXt  # noqa: E402,F401
 from .map_pit import MAP_PiT  # noqa: E402,F401
+from . import pit  # noqa: E402,F401  (registers the baseline name pit_s)
+from .pit import PiT  # noqa: E402,F401
 from . import mobilenet  # noqa: E402,F401  (registers the extra names mobilenet_v1 / map_mobilenet_v1)
 from .mobilenet import MobileNetV1  # noqa: E402,F401
 from . import map_resnet  # noqa: E402,F401  (registers the repaired name map_resnet50)

@@ -387,6 +387,74 @@ __global__ __launch_bounds__(256) void rows_bcast_kernel(const T* __restrict__ s
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// global average pool over the tokens of the last stage (the pool_type='gap' head of map_pit.py:194, `x[-1].mean([-2, -1])`) and
+// its backward.  V consecutive channels per lane: V = 16 bytes' worth (8 bf16 / 4 fp32) when C is a multiple of it, V = 1 otherwise.
+// A "column" is one V-channel piece of one sample; the 64 lanes of a wave hold 64 consecutive columns (1 KiB per token row on the
+// vector path), the 4 waves of a workgroup take the token rows n = wave, wave + 4, ...
+// ------------------------------------------------------------------------------------------------------------------
+template <typename T, int V> __device__ __forceinline__ void ldv(const T* p, float v[V]) {
+    if constexpr (V == 8) load8(p, v);
+    else if constexpr (V == 4) load4(p, v);
+    else v[0] = elt<T>::ld(p);
+}
+template <typename T, int V> __device__ __forceinline__ void stv(T* p, const float v[V]) {
+    if constexpr (V == 8) store8(p, v);
+    else if constexpr (V == 4) store4(p, v);
+    else elt<T>::st(p, v[0]);
+}
+
+// y[b][c] = (1/N) sum_n x[b][n][c].  fp32 accumulation in a fixed order: every wave sums its rows in ascending n, the four partial
+// sums are added as ((w0 + w1) + w2) + w3 through LDS; no atomics.  ncol = B * C / V, CV = C / V.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void token_gap_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, long ncol, int N, int CV, float inv) {
+    __shared__ float part[3][64][V];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (long g0 = (long)blockIdx.x * 64; g0 < ncol; g0 += (long)gridDim.x * 64) {      // g0 is uniform over the workgroup
+        const long g = g0 + lane;
+        float acc[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) acc[j] = 0.f;
+        if (g < ncol) {
+            const long b = g / CV, ch = g % CV;
+            const T* p = x + (b * N * CV + ch) * V;
+            for (int n = wv; n < N; n += 4) {
+                float v[V];
+                ldv<T, V>(p + (long)n * CV * V, v);
+#pragma unroll
+                for (int j = 0; j < V; ++j) acc[j] += v[j];
+            }
+        }
+        if (wv > 0) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) part[wv - 1][lane][j] = acc[j];
+        }
+        __syncthreads();
+        if (wv == 0 && g < ncol) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) acc[j] = (((acc[j] + part[0][lane][j]) + part[1][lane][j]) + part[2][lane][j]) * inv;
+            stv<T, V>(y + g * V, acc);
+        }
+        __syncthreads();
+    }
+}
+
+// dx[b][n][c] = dy[b][c] / N: one correctly rounded fp32 division per column, then the rounding of the store
+template <typename T, int V>
+__global__ __launch_bounds__(256) void token_gap_bwd_kernel(const T* __restrict__ dy, T* __restrict__ dx, long ncol, int N, int CV) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const float fn = (float)N;
+    for (long g = (long)blockIdx.x * 64 + lane; g < ncol; g += (long)gridDim.x * 64) {
+        const long b = g / CV, ch = g % CV;
+        float v[V];
+        ldv<T, V>(dy + g * V, v);
+#pragma unroll
+        for (int j = 0; j < V; ++j) v[j] = __fdiv_rn(v[j], fn);
+        T* p = dx + (b * N * CV + ch) * V;
+        for (int n = wv; n < N; n += 4) stv<T, V>(p + (long)n * CV * V, v);
+    }
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 bool fast_path() {       // GAEXT_DWPOOL_SIMPLE=1: the plain any-multiplier kernels (diagnostics / tests)
     return !GA_KNOB("DWPOOL_SIMPLE", 0);
@@ -499,4 +567,42 @@ extern "C" int ga_rows_bcast(const void* src, void* dst, int B, int HW, int C, f
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     PIT_DISPATCH(dtype, rows_bcast_kernel, grid_for((long)B * HW * C / 8), s, (const T*)src, (T*)dst, B, HW, C, scale);
     return ga_check_launch("ga_rows_bcast");
+}
+
+// 16-byte pieces when the row length allows them and every pointer is aligned, single elements otherwise
+#define PIT_GAP_DISPATCH(dtype, KERNEL, vec, grid, s, ...)                                                                  \
+    do {                                                                                                                    \
+        if ((dtype) == GA_BF16) {                                                                                           \
+            using T = bf16_t;                                                                                               \
+            if (vec) hipLaunchKernelGGL((KERNEL<T, 8>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);                          \
+            else hipLaunchKernelGGL((KERNEL<T, 1>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);                              \
+        } else {                                                                                                            \
+            using T = float;                                                                                                \
+            if (vec) hipLaunchKernelGGL((KERNEL<T, 4>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);                          \
+            else hipLaunchKernelGGL((KERNEL<T, 1>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);                              \
+        }                                                                                                                   \
+    } while (0)
+
+extern "C" int ga_token_gap_fwd(const void* x, void* y, int B, int N, int C, int dtype, ga_stream_t stream) {
+    GA_REQUIRE(x && y && B > 0 && N > 0 && N <= (1 << 24) && C > 0 && (dtype == GA_BF16 || dtype == GA_F32), "ga_token_gap_fwd: bad args");
+    const int V = dtype == GA_BF16 ? 8 : 4;
+    const bool vec = C % V == 0 && aligned16(x) && aligned16(y);
+    const int CV = vec ? C / V : C;
+    const long ncol = (long)B * CV;
+    const int grid = (int)std::min<long>(2048, (ncol + 63) / 64);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PIT_GAP_DISPATCH(dtype, token_gap_fwd_kernel, vec, grid, s, (const T*)x, (T*)y, ncol, N, CV, 1.0f / (float)N);
+    return ga_check_launch("ga_token_gap_fwd");
+}
+
+extern "C" int ga_token_gap_bwd(const void* dy, void* dx, int B, int N, int C, int dtype, ga_stream_t stream) {
+    GA_REQUIRE(dy && dx && B > 0 && N > 0 && N <= (1 << 24) && C > 0 && (dtype == GA_BF16 || dtype == GA_F32), "ga_token_gap_bwd: bad args");
+    const int V = dtype == GA_BF16 ? 8 : 4;
+    const bool vec = C % V == 0 && aligned16(dy) && aligned16(dx);
+    const int CV = vec ? C / V : C;
+    const long ncol = (long)B * CV;
+    const int grid = (int)std::min<long>(2048, (ncol + 63) / 64);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    PIT_GAP_DISPATCH(dtype, token_gap_bwd_kernel, vec, grid, s, (const T*)dy, (T*)dx, ncol, N, CV);
+    return ga_check_launch("ga_token_gap_bwd");
 }

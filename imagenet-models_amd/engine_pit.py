@@ -10,10 +10,14 @@ pool_type='map', :84-201) feeding the MAP head (engine_map.MAPEngine).
   forward_features' list (:185-201) -> MAPHead (:133-144) ......... MultiScale at the level-2 map's size: the two 27 x 27 maps
                                                                     through ga_resize_concat_* (general bilinear), the 14 x 14 one
                                                                     copied, the 7 x 7 one enlarged (ga_pool_concat_*)
+
+PiTEngine: the same trunk plan under the plain head of pool_type != 'map' (:148, :194): ga_token_gap_fwd over the last stage's tokens,
+Linear (ga_gemm, fp32 logits); backward: classifier weight gradient / dgrad, ga_token_gap_bwd as the only seed of the trunk.
 """
 import torch
 
 from . import ops  # noqa: F401
+from .engine import GAEngine, pad8
 from .engine_vit import MAPViTEngine
 
 
@@ -28,7 +32,9 @@ class MAPPiTEngine(MAPViTEngine):
                 i += 1
         return out
 
-    def _build(self):
+    def _build_pit_trunk(self):
+        """conv_embedding + pos_embed and the three transformer stages with their pooling convolutions (forward_features, :173-188);
+        returns the feature list [(map, side, channels)] = [embedding, stage 0, stage 1, stage 2] and the patch row length"""
         cfg = self.cfg
         B, T, F, dt, P = self.B, self.training, self.fwd, self.dt, self.P
         self.img = img = self._img
@@ -75,6 +81,12 @@ class MAPPiTEngine(MAPViTEngine):
                     x, hw = y, ho
         self._chain = None
         F.lane = 0
+        return feats, K0
+
+    def _build(self):
+        cfg = self.cfg
+        B, T, F, dt = self.B, self.training, self.fwd, self.dt
+        feats, K0 = self._build_pit_trunk()
         # ---------------- MultiScale at the size of feature `multi_scale_level` (map.py:322-333) ----------------
         Hc = self.Hc = feats[cfg['multi_scale_level']][1]
         M4 = B * Hc * Hc
@@ -105,8 +117,7 @@ class MAPPiTEngine(MAPViTEngine):
         self.prep.flush('prep.')
 
     def _build_pit_backward(self, xh, M4, K0):
-        Bk, dt, P, cfg, B = self.bwd, self.dt, self.P, self.cfg, self.B
-        dims, depth, w0 = cfg['dims'], cfg['depth'], cfg['width']
+        Bk, dt, B = self.bwd, self.dt, self.B
         dcat = self._build_head_backward(xh, M4)
         ctot = self.ms['ctot']
         seeds = []
@@ -117,6 +128,13 @@ class MAPPiTEngine(MAPViTEngine):
             else:
                 Bk.pool_concat_bwd(dcat, None, ds, B, fhw, fhw, c, self.Hc, self.Hc, ctot, off, mode, dt, label=f'agg.b{off}')
             seeds.append(ds)
+        self._build_pit_trunk_backward(seeds, K0)
+
+    def _build_pit_trunk_backward(self, seeds, K0):
+        """seeds[i]: gradient wrt feature i of _build_pit_trunk's list (None: the head does not read that feature); seeds[3], the
+        gradient wrt the last stage's output, is always there"""
+        Bk, dt, P, cfg, B = self.bwd, self.dt, self.P, self.cfg, self.B
+        dims, depth, w0 = cfg['dims'], cfg['depth'], cfg['width']
         # sequence gradients rotate through three buffers (the asynchronous weight gradients still read the one before); they are
         # sized for the largest stage and viewed per stage
         nmax = max(B * hw * hw * C for _, _, hw, C in self.stage_io)
@@ -142,7 +160,8 @@ class MAPPiTEngine(MAPViTEngine):
                                          hwp, Cp, mult, dt, label=f'pools.{s - 1}.wg')
                 dprev = self.buf(f'pool.{s - 1}.dx', (B * hwp * hwp, Cp))
                 Bk.dwpool_bwd_data(dy, P[f'pools.{s - 1}.conv.weight'], dprev, B, hwp, hwp, Cp, mult, dt, label=f'pools.{s - 1}.dg')
-                Bk.copy2d(seeds[s], hwp * hwp * Cp, dprev, hwp * hwp * Cp, B, hwp * hwp * Cp, dt, accumulate=True, label=f'feat.{s}.b')
+                if seeds[s] is not None:
+                    Bk.copy2d(seeds[s], hwp * hwp * Cp, dprev, hwp * hwp * Cp, B, hwp * hwp * Cp, dt, accumulate=True, label=f'feat.{s}.b')
                 dy = dprev
                 # transformers.s and pools.(s-1) are final only after the pooling conv's weight gradient (asynchronous lane) and the
                 # deferred unfold jobs of the stage's blocks: join + flush BEFORE the mark the gradient buckets key on
@@ -151,10 +170,51 @@ class MAPPiTEngine(MAPViTEngine):
                 Bk.flush(f'stage{s + 1}.')
                 Bk.mark(f'stage{s + 1}')
         # dy: gradient wrt x0 from stage 0; x0 is also feature 0
-        Bk.copy2d(seeds[0], w0 * w0 * dims[0], dy, w0 * w0 * dims[0], B, w0 * w0 * dims[0], dt, accumulate=True, label='feat.0.b')
+        if seeds[0] is not None:
+            Bk.copy2d(seeds[0], w0 * w0 * dims[0], dy, w0 * w0 * dims[0], B, w0 * w0 * dims[0], dt, accumulate=True, label='feat.0.b')
         dposT = self.tmp('dposT', (w0 * w0, dims[0]), torch.float32)
         Bk.pos_add_bwd(dy, dposT, B, w0 * w0, dims[0], dt, label='embedb')
         Bk.transpose_f32(dposT, self.grad('pos_embed'), w0 * w0, dims[0], accumulate=True)
         with self._wlane():
             Bk.wgrad(dy, self.patches, self.grad('patch_embed.conv.weight'), B * w0 * w0, dims[0], K0, dt,
                      dbias=self.grad('patch_embed.conv.bias'), label='patch.wg')
+
+
+class PiTEngine(MAPPiTEngine):
+    def _build(self):
+        cfg = self.cfg
+        B, T, F, dt, P = self.B, self.training, self.fwd, self.dt, self.P
+        NC = cfg['num_classes']
+        assert NC % 8 == 0, 'num_classes must be a multiple of 8 (pad the classifier)'
+        self.drop = None
+        self.G = 1
+        feats, K0 = self._build_pit_trunk()
+        x3, hw, C = feats[-1]                                 # forward_head reads the last feature only (:194)
+        N = hw * hw
+        pool = self.act('head.pool', (B, C))
+        F.token_gap_fwd(x3, pool, B, N, C, dt, label='head.pool')
+        Wh = self._w_plain('head.weight', NC, C, 1, 1)
+        self.logits = self.buf('logits', (1, B, NC), torch.float32)
+        F.gemm(pool, Wh, self.logits[0], B, NC, C, dt, bias=P['head.bias'], c_f32=True, label='head.fc')
+        if T:
+            Bk = self.bwd
+            self.dlogits = self.buf('dlogits', (1, B, NC))
+            dl = self.dlogits[0]
+            with self._wlane():
+                Bk.wgrad(dl, pool, self.grad('head.weight'), B, NC, C, dt, dbias=self.grad('head.bias'), label='head.wg')
+            dpool = self.tmp('head.dpool', (B, C))
+            Bk.gemm(dl, self.W['head.weight.T'], dpool, B, C, NC, dt, ldb=pad8(NC), label='head.dg')
+            seed = self.buf('head.seed', (B * N, C))
+            Bk.token_gap_bwd(dpool, seed, B, N, C, dt, label='head.poolb')
+            if self.async_wgrad:
+                Bk.join_async()
+            Bk.flush('heads.')
+            Bk.mark('heads')
+            self._build_pit_trunk_backward([None, None, None, seed], K0)
+            if self.async_wgrad:
+                Bk.join_async()
+            Bk.flush('end.')
+        self.prep.flush('prep.')
+
+    def _loss_operands(self):
+        return GAEngine._loss_operands(self)

@@ -386,6 +386,12 @@ class Plan:
     def rows_bcast(self, src, dst, B, HW, Cdim, scale, dtype, label=None):
         self._add('ga_rows_bcast', (_ptr(src), _ptr(dst), B, HW, Cdim, scale, dtype), label, keep=(src, dst))
 
+    def token_gap_fwd(self, x, y, B, N, Cdim, dtype, label=None):
+        self._add('ga_token_gap_fwd', (_ptr(x), _ptr(y), B, N, Cdim, dtype), label, keep=(x, y))
+
+    def token_gap_bwd(self, dy, dx, B, N, Cdim, dtype, label=None):
+        self._add('ga_token_gap_bwd', (_ptr(dy), _ptr(dx), B, N, Cdim, dtype), label, keep=(dy, dx))
+
     def vit_embed_fwd(self, tok, cls, pos, x0, B, Np, Cdim, dtype, label=None):
         self._add('ga_vit_embed_fwd', (_ptr(tok), _ptr(cls), _ptr(pos), _ptr(x0), B, Np, Cdim, dtype), label, keep=(tok, cls, pos, x0))
 

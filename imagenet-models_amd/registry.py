@@ -15,6 +15,10 @@ _extra = set()
 # Like the extra tier they are reachable through every lookup and left out of list_models() (include_extra=True too) unless
 # include_repaired=True.
 _repaired = set()
+# "baseline" names: the plain counterpart the reference registers beside a MAP model whose family joined the engine after the default
+# list was pinned (pit_s, the pool_type='gap' PoolingTransformer that map_pit_s is measured against).  Reachable through every lookup,
+# left out of list_models() -- with include_extra / include_repaired too -- unless include_baseline=True.
+_baseline = set()
 
 
 def register_model(fn, name=None):
@@ -48,11 +52,23 @@ def is_repaired(name):
     return name in _repaired
 
 
+def register_baseline_model(fn, name=None):
+    """register_model for a "baseline" name (see _baseline): reachable through every lookup, listed only with include_baseline=True"""
+    register_model(fn, name)
+    _baseline.add(name or fn.__name__)
+    return fn
+
+
+def is_baseline(name):
+    return name in _baseline
+
+
 def _unregister(name):
     _entrypoints.pop(name, None)
     _unsupported.pop(name, None)
     _extra.discard(name)
     _repaired.discard(name)
+    _baseline.discard(name)
 
 
 def is_model(name):
@@ -67,12 +83,13 @@ def is_supported(name):
     return name in _entrypoints and name not in _unsupported
 
 
-def list_models(filter='', include_unsupported=False, include_extra=False, include_repaired=False):
+def list_models(filter='', include_unsupported=False, include_extra=False, include_repaired=False, include_baseline=False):
     """names the HIP engine can run; include_unsupported adds the ones that only construct (parameter layout, checkpoints),
-    include_extra the "extra" names (mobilenet_v1, map_mobilenet_v1), include_repaired the "repaired" ones (map_resnet50); every
-    other lookup treats those like any name"""
+    include_extra the "extra" names (mobilenet_v1, map_mobilenet_v1), include_repaired the "repaired" ones (map_resnet50),
+    include_baseline the "baseline" ones (pit_s); every other lookup treats those like any name"""
     return sorted(n for n in _entrypoints if filter in n and (include_unsupported or n not in _unsupported)
-                  and (include_extra or n not in _extra) and (include_repaired or n not in _repaired))
+                  and (include_extra or n not in _extra) and (include_repaired or n not in _repaired)
+                  and (include_baseline or n not in _baseline))
 
 
 def model_entrypoint(name):

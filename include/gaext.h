@@ -718,6 +718,14 @@ int ga_resize_concat_bwd(const void* dcat, void* dsrc, int B, int Hin, int Win, 
 /* dst[b][p][:] = scale * src[b][:], p < HW: the gradient of the global average pool of the plain ConvNeXt head
  * (MAP/models/map_convnext.py:134-135, `x.mean([-2, -1])`; scale = 1 / HW) */
 int ga_rows_bcast(const void* src, void* dst, int B, int HW, int C, float scale, int dtype, ga_stream_t stream);
+/* global average pool over the tokens of a [B][N][C] sequence: the pool_type='gap' head of the plain PiT
+ * (MAP/models/map_pit.py:194, `x[-1].mean([-2, -1])`).  x, y, dy, dx are of the activation dtype.
+ *   ga_token_gap_fwd: y[b][c] = (1/N) * sum_n x[b][n][c]; fp32 accumulation in a fixed order, no atomics: bitwise repeatable
+ *   ga_token_gap_bwd: dx[b][n][c] = dy[b][c] / N (overwrites dx): a correctly rounded fp32 quotient, then the rounding of the store
+ * 16-byte loads and stores when C is a multiple of 8 (bf16) / 4 (fp32) and the pointers are 16-byte aligned; any other C or
+ * alignment runs the one-element form of the same kernels.  N <= 2^24. */
+int ga_token_gap_fwd(const void* x, void* y, int B, int N, int C, int dtype, ga_stream_t stream);
+int ga_token_gap_bwd(const void* dy, void* dx, int B, int N, int C, int dtype, ga_stream_t stream);
 
 /* small fp32 / elementwise utilities */
 int ga_memset(void* p, int value, size_t bytes, ga_stream_t stream); /* hipMemsetAsync on `stream` */
