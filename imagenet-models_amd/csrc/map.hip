@@ -276,9 +276,12 @@ __global__ __launch_bounds__(512) void mt_attn_bwd_kernel(const T* __restrict__ 
 // ------------------------------------------------------------------------------------------------------------------
 // `interactive` class attention (map.py:96-98,130-136): two linears over the HEAD axis around the softmax,
 //     S = scale q k^T;  U = S + W1 S + b1;  A = softmax_n(U);  Pm = A + W2 A + b2;  D = Pm * mask;  out = D v
-// (W1, W2 [heads][heads], the "S" / "A" above indexed [head][key]).  Used by the MAP heads of map_resnet50 / map_mobilenet_v1 /
-// map_faster_vit_3_224; none of the registered in-scope models turns it on, so these kernels are written for clarity, not
-// speed: one workgroup per sample, fp32 in LDS, a thread per (head, key) for the head mixing, a wave per head for the softmax.
+// (W1, W2 [heads][heads], the "S" / "A" above indexed [head][key]).  The registered map_resnet50 (T = 5: four Gram tokens and
+// the self-distillation token; 12 heads of 32) and map_mobilenet_v1 (T = 4, 6 heads of 32) run this pair on every step, over
+// N = T + 49 keys at 224 x 224.
+// Written for clarity, not speed: one workgroup per sample, fp32 in LDS, a thread per (head, key) for the head mixing, a wave
+// per head for the softmax.  Every operand is read and written element by element: any hd >= 1, any tok_ld / dtok_ld >= 2E,
+// no alignment beyond that of the element type.
 // Saved for backward: P = A (the softmax output), as in the plain kernels.
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int kIaThr = 256;
@@ -610,8 +613,9 @@ extern "C" int ga_class_attn_mt_bwd(const void* dout, const void* q, const void*
     GA_REQUIRE(dout && q && kv_cls && kv_tok && P && dq && dkv_cls && dkv_tok && B > 0 && T_ >= 1 && T_ <= kMaxT && N > T_,
                "ga_class_attn_mt_bwd: bad args (T <= %d)", kMaxT);
     const int E = heads * hd;
-    GA_REQUIRE(hd % 8 == 0 && E <= 512 && tok_ld >= 2 * E && dtok_ld >= 2 * E && tok_ld % 8 == 0 && dtok_ld % 8 == 0,
-               "ga_class_attn_mt_bwd: needs head_dim %% 8 == 0, heads*head_dim <= 512");
+    GA_REQUIRE(hd % 8 == 0 && E <= 512 && tok_ld >= 2 * E && dtok_ld >= 2 * E && tok_ld % 8 == 0 && dtok_ld % 8 == 0 && al16(dout) &&
+                   al16(q) && al16(kv_cls) && al16(kv_tok) && al16(dkv_cls) && al16(dkv_tok),
+               "ga_class_attn_mt_bwd: needs head_dim %% 8 == 0, heads*head_dim <= 512, 16-byte aligned rows");
     const size_t lds = mt_lds(T_, N, heads, hd, true);
     GA_REQUIRE(lds <= 160 * 1024, "ga_class_attn_mt_bwd: %zu B of LDS needed", lds);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -649,7 +653,7 @@ extern "C" int ga_class_attn_mt_ia_bwd(const void* dout, const void* q, const vo
                                        void* dkv_tok, int64_t dtok_ld, float* dW1, float* db1, float* dW2, float* db2, int B, int T_, int N,
                                        int heads, int hd, float scale, int dtype, ga_stream_t stream) {
     GA_REQUIRE(dout && q && kv_cls && kv_tok && P && W1 && W2 && b2 && dq && dkv_cls && dkv_tok && dW1 && db1 && dW2 && db2 && B > 0 && T_ >= 1 &&
-                   T_ <= kMaxT && N > T_, "ga_class_attn_mt_ia_bwd: bad args (T <= %d)", kMaxT);
+                   T_ <= kMaxT && N > T_ && heads >= 1 && hd >= 1, "ga_class_attn_mt_ia_bwd: bad args (T <= %d)", kMaxT);
     GA_REQUIRE(tok_ld >= 2 * heads * hd && dtok_ld >= 2 * heads * hd, "ga_class_attn_mt_ia_bwd: row strides");
     const size_t lds = (size_t)(2 * T_ + 4) * heads * N * sizeof(float);
     GA_REQUIRE(lds <= 160 * 1024, "ga_class_attn_mt_ia_bwd: %zu B of LDS needed", lds);

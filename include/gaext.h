@@ -503,10 +503,13 @@ int ga_conv3s2_dgrad_prep(const float* w, void* out, int Co, int Ci, int64_t ldo
  *       entry t is stored at (t % ntok) * (ntri / ntok) + t / ntok before the grouped layout is applied (ntok = 1: identity).
  *   ga_map_tokens_fwd: e [B][C*T] (channel c*T + t, the bp_reduction output, map.py:231-232) -> tok [B][T (+1)][C];
  *       add_mean: the extra row is the mean over the T tokens (CAP's self-distillation token, map.py:273-275).  _bwd: its transpose.
- *   ga_class_attn_mt_*: ClassAttention with T <= 4 query tokens (map.py:118-144, in_dim == dim branch; `interactive`: ga_class_attn_mt_ia_* below):
- *       q [B][T][E], kv_cls [B][T][2E] (k | v of the class rows), kv_tok = k | v rows of the N - T image tokens (row stride
+ *   ga_class_attn_mt_*: ClassAttention with 1 <= T <= 8 query tokens (map.py:118-144, in_dim == dim branch; `interactive`: ga_class_attn_mt_ia_* below):
+ *       q [B][T][E], kv_cls [B][T][2E] (k | v of the class rows), kv_tok = k | v rows of the N - T >= 1 image tokens (row stride
  *       tok_ld); P [B][T][heads][N] fp32 = softmax, saved; mask (fp32, same shape, or NULL) = attention dropout mask
  *       (already divided by keep); out [B][T][E].  bwd overwrites dq, dkv_cls and the dkv_tok rows (stride dtok_ld).
+ *       Requires hd % 8 == 0, E = heads * hd <= 512, tok_ld / dtok_ld >= 2E and multiples of 8, q, kv_cls, kv_tok (and in _bwd
+ *       dout, dkv_cls, dkv_tok) 16-byte aligned, and an LDS working set of at most 160 KiB:
+ *       4 (N E / 8 + c T heads N + 16 E) bytes, c = 1 forward, 2 backward.  GA_ERR_BAD_ARG otherwise, nothing is launched.
  *   ga_map_loss_fwd_bwd: MAP/train.py:792-839 (distill_tokens == 0): ga_loss_fwd_bwd on the org logits plus, per group,
  *       KL_sum(log_softmax(avg_k) || log_softmax(org_k).detach()) / (B*NC); davg = its gradient (avg == NULL: the GA loss).
  *   ga_gelu_fwd / _bwd: y = gelu(x) (erf), dx = dy * gelu'(x)   (MultiScale ConvNormAct with non_linearity = GELU, map.py:331)
@@ -525,7 +528,11 @@ int ga_class_attn_mt_bwd(const void* dout, const void* q, const void* kv_cls, co
                          int heads, int hd, float scale, int dtype, ga_stream_t stream);
 /* ClassAttention with `interactive` = True (map.py:96-98,130-136): W1, W2 [heads][heads] + b1, b2 [heads] fp32 mix the HEADS of
  * the scores before and of the probabilities after the softmax: U = S + W1 S + b1, A = softmax(U), Pm = A + W2 A + b2.
- * Same operand layouts as ga_class_attn_mt_*; P saves A.  _bwd also ACCUMULATES dW1, db1, dW2, db2 (fp32). */
+ * out = (Pm * mask) v.  Same operand layouts as ga_class_attn_mt_*; P saves A.  _bwd overwrites dq, dkv_cls and the dkv_tok rows
+ * and ACCUMULATES dW1, db1, dW2, db2 (fp32 atomics: the caller zeroes them).  These kernels access every operand element by
+ * element, so their requirements are weaker than the plain pair's: 1 <= T <= 8, N > T, any heads, hd >= 1 (hd % 8 and E <= 512
+ * are NOT required), tok_ld / dtok_ld >= 2E with no multiple-of-8 rule, pointers aligned to their element type only, and an LDS
+ * working set of at most 160 KiB: 4 * 2 heads N bytes forward, 4 (2T + 4) heads N bytes backward.  GA_ERR_BAD_ARG otherwise. */
 int ga_class_attn_mt_ia_fwd(const void* q, const void* kv_cls, const void* kv_tok, int64_t tok_ld, void* out, float* P,
                             const float* mask, const float* W1, const float* b1, const float* W2, const float* b2, int B, int T, int N,
                             int heads, int hd, float scale, int dtype, ga_stream_t stream);
