@@ -81,7 +81,9 @@ class MlpDesc(C.Structure):
 class MlpBwdDesc(C.Structure):
     _fields_ = [('X', vp), ('ldx', i64), ('DY', vp), ('lddy', i64), ('W1', vp), ('ldw1', i64), ('b1', vp),
                 ('W2T', vp), ('ldw2t', i64), ('W1T', vp), ('ldw1t', i64), ('A', vp), ('lda', i64), ('DH', vp), ('lddh', i64),
-                ('DX', vp), ('lddx', i64), ('M', i64), ('C', i32), ('H', i32), ('dtype', i32)]
+                ('DX', vp), ('lddx', i64), ('M', i64), ('C', i32), ('H', i32), ('dtype', i32),
+                # optional: fc1 weight gradient accumulated inside the kernel (include/gaext.h)
+                ('dW1', vp), ('ldw', i64), ('db1', vp), ('partials', vp), ('partials_bytes', C.c_size_t), ('max_blocks', i32)]
 
 
 class SmallLinearDesc(C.Structure):
@@ -234,6 +236,8 @@ _SIGS = {
     'ga_mlp_supported': ([i32, i32, i32], i32),
     'ga_mlp_fwd': ([C.POINTER(MlpDesc), vp], i32),
     'ga_mlp_bwd': ([C.POINTER(MlpBwdDesc), vp], i32),
+    'ga_mlp_bwd_wgrad_supported': ([i32, i32, i32], i32),
+    'ga_mlp_bwd_partials': ([C.POINTER(MlpBwdDesc)], C.c_size_t),
     'ga_memset': ([vp, i32, C.c_size_t, vp], i32),
     'ga_transpose_f32': ([vp, vp, i32, i32, i32, vp], i32),
     'ga_axpy_f32': ([vp, vp, f32, i64, vp], i32),
@@ -281,7 +285,7 @@ def config_string():
     # the host-side scheduling switches the engines read from the environment when they are built (engine.py: lanes, chains)
     host = sorted(k for k in os.environ if k.startswith(('GAEXT_', 'GA_FUSED_MLP')) and k != 'GAEXT_LIB')
     known = {'GAEXT_ASYNC_WGRAD', 'GAEXT_FWD_SPLIT', 'GAEXT_PAR_BRANCH', 'GAEXT_FWD_SKEW', 'GAEXT_FUSE_DP', 'GAEXT_HEAD_STREAMS',
-             'GA_FUSED_MLP', 'GAEXT_SMALL_SINGLE', 'GAEXT_SYNC_DEBUG'}
+             'GA_FUSED_MLP', 'GAEXT_SMALL_SINGLE', 'GAEXT_SYNC_DEBUG', 'GAEXT_MLP_WG1'}
     for k in host:
         if k in known:
             s += f' host:{k}={os.environ[k]}'

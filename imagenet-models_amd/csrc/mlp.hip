@@ -35,22 +35,23 @@ __device__ __forceinline__ bf16x8_t frag(const unsigned char* slab, int r0, int 
 }
 
 // global rows [row0, row0 + ROWS) x (32 * KS) bf16 -> KS slabs of [ROWS][64 B]; rows >= limit are zero.  All the loads of a
-// thread are issued before the first LDS write (one exposed latency, not one per piece).
+// thread are issued before the first LDS write (one exposed latency, not one per piece).  tid = threadIdx.x (a parameter so
+// that the persistent backward can keep this addressing out of the registers that live across its tiles).
 template <int ROWS, int KS, int NTHR>
-__device__ __forceinline__ void stage_rows(unsigned char* dst, const bf16_t* src, long ld, long row0, long limit) {
+__device__ __forceinline__ void stage_rows(unsigned char* dst, const bf16_t* src, long ld, long row0, long limit, int tid) {
     constexpr int CPR = KS * 4, NP = ROWS * CPR / NTHR;
     static_assert(ROWS * CPR % NTHR == 0, "tile must split evenly over the threads");
     u32x4_t v[NP];
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-        const int idx = threadIdx.x + NTHR * i;
+        const int idx = tid + NTHR * i;
         const int r = idx / CPR, c = idx - r * CPR;
         v[i] = u32x4_t{0, 0, 0, 0};
         if (row0 + r < limit) v[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(src + (row0 + r) * ld + c * 8));
     }
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
-        const int idx = threadIdx.x + NTHR * i;
+        const int idx = tid + NTHR * i;
         const int r = idx / CPR, c = idx - r * CPR;
         *reinterpret_cast<u32x4_t*>(dst + (c >> 2) * ROWS * 64 + slab_off(r, c & 3)) = v[i];
     }
@@ -83,10 +84,10 @@ __device__ __forceinline__ void rows_prefetch(PreArr<C, NTHR>& v, const bf16_t* 
 template <int C, int NTHR, int NWM, int TM>
 __device__ __forceinline__ void store_rows(float* Cs, const f32x4_t (&acc)[C / 32][TM], int wm, int wn, int lane, long m0, long M,
                                            const float* bias, const float* rowscale, int rps, bool has_r,
-                                           const PreArr<C, NTHR>& pre, bf16_t* Y, long ldy) {
+                                           const PreArr<C, NTHR>& pre, bf16_t* Y, long ldy, int tid) {
     constexpr int LDC = C + 4, P8 = C / 8, RG = NTHR / P8, WROWS = 16 * TM, WPH = 64 / WROWS;   // waves (in m) per 64-row piece
     constexpr int NR = (64 + RG - 1) / RG;
-    const int c8 = threadIdx.x % P8, rg = threadIdx.x / P8;
+    const int c8 = tid % P8, rg = tid / P8;
     float bv[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) bv[j] = bias ? bias[c8 * 8 + j] : 0.f;
@@ -184,7 +185,7 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_kernel(const ga_mlp_desc d) {
     };
 
     w_load(0);
-    stage_rows<BM, KS1, 256>(Xs, reinterpret_cast<const bf16_t*>(d.X), d.ldx, m0, d.M);
+    stage_rows<BM, KS1, 256>(Xs, reinterpret_cast<const bf16_t*>(d.X), d.ldx, m0, d.M, tid);
     for (int i = tid; i < 4 * C; i += 256) B1s[i] = d.b1[i];
     w1_store();
     w2_store();
@@ -257,7 +258,7 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_kernel(const ga_mlp_desc d) {
     round(d.H - HC, false);
     // (the last barrier of the round has passed: every LDS operand is dead)
     store_rows<C, 256, 2, 4>(reinterpret_cast<float*>(smem), y, wm, wn, lane, m0, d.M, d.b2, d.rowscale, d.rows_per_scale,
-                             d.R != nullptr, rpre, reinterpret_cast<bf16_t*>(d.Y), d.ldy);
+                             d.R != nullptr, rpre, reinterpret_cast<bf16_t*>(d.Y), d.ldy, tid);
 }
 
 template <int C, int HC> constexpr int fwd_lds() {
@@ -272,14 +273,49 @@ template <int C, int HC> constexpr int fwd_lds() {
 //   P1: h = Xs . W1s^T,  t = Ds . W2Ts^T   (K = C; wave: 32 rows x HC/2 each)
 //       a = gelu(h + b1) -> A2s,  dh = t * gelu'(h + b1) -> DHs
 //   P2: dx[128 x C] += DHs . W1Ts^T (K = HC; wave: 32 rows x C/2);  A2s / DHs rows -> global with 16-byte stores
+//       (a NULL A / DH: that tile is not stored)
 // (measured at C = 96, M = 802816: 0.54 ms; a 4-wave / two-workgroup form writing a / dh as 8-byte pieces straight from the
 //  accumulators: 1.06 ms -- the 32-byte runs cost more than the LDS staging)
+//
+// WG (desc.dW1 given, C = 96 only): the fc1 weight gradient dW1 += DH^T . X and db1 += colsum(DH) are accumulated here, from
+// the DHs / Xs images that are in LDS anyway, so DH need not go to HBM and come back for a ga_wgrad launch.  The launch is then
+// persistent: workgroup b walks the 128-row tiles b, b + grid, ... and keeps ONE accumulator set through all of them:
+//   P2 also: dW1[j0 .. j0+HC)[0 .. C) += DHs^T . Xs (K = the tile's 128 token rows): 4 x 6 output tiles of 16 x 16 per chunk,
+//       wave w owns hidden tile w >> 1 and channel tiles 3 (w & 1) .. +2, 4 k-steps of 32 rows.  Both operands are read
+//       k-strided (rows = reduction index) out of the [row][64 B] slab images with ds_read_b64_tr_b16; db1 from the same DH
+//       fragments (dot against ones, the TN GEMM's form), so it sums exactly the bf16 values the product multiplies.
+//   Rows >= M of the last tile add nothing: stage_rows zero-fills Xs and Ds there, so t = 0 and dh = t * gelu' = 0.
+//   The accumulators dw[chunk][3] (H / HC = 6 chunks, 72 VGPRs, + 6 for db1) are indexed statically: a scalar branch per chunk.
+//   After its last tile the workgroup stores its fp32 partial [H*C + H] to part[b]; mlp_bwd_wg_reduce_kernel adds the
+//   partials in workgroup order into dW1 / db1 (no float atomics: two runs give the same bits).
+//   mlp_bwd_kernel<96, 64, true> (-Rpass-analysis=kernel-resource-usage): 241 VGPRs, 0 AGPRs, no VGPR / SGPR spill, no scratch,
+//   2 waves per SIMD (the plain form: 158 VGPRs).  The rolled chunk loop and the laundered thread indices below are what keep it
+//   there: unrolled six times the kernel spilled 239 registers, with running row pointers kept across the walk 45.
 // =================================================================================================================
-template <int C, int HC>
+// byte offset, inside one [rows][64 B] slab, of this lane's piece of the transposed 4-row x 16-column block read
+// (ds_read_b64_tr_b16: lane 4q + p of a 16-lane group supplies row q, columns 4p .. 4p+3 and receives column i of the 4 rows).
+// Lane group g reads reduction rows 8g + 4hf .. +3 of a 32-row k-step: with hf = 0, 1 a lane ends up with rows 8g .. 8g+7 of
+// column (lane & 15), the 16x16x32 operand.  u0 = first 16-byte unit of the 16 columns (0 or 2).  The swizzle term
+// ((row >> 2) & 3) = (2g + hf) & 3 flips unit bits per lane group AND per half, so each (hf, u0) has an address of its own;
+// k-steps (+ 32 rows) are a constant 2048 bytes apart.
+__device__ __forceinline__ unsigned tr_off(int lane, int hf, int u0) {
+    const int i = lane & 15, row = 8 * (lane >> 4) + 4 * hf + (i >> 2);
+    return slab_off(row, u0 + ((i & 3) >> 1)) + 8 * (i & 1);
+}
+__device__ __forceinline__ bf16x8_t tr_frag(const unsigned char* lo, const unsigned char* hi) {
+    s16x4_t v[2];
+    v[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)lo);
+    v[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)hi);
+    return *reinterpret_cast<const bf16x8_t*>(&v[0]);
+}
+
+template <int C, int HC, bool WG>
 __global__ __launch_bounds__(512, 1) void mlp_bwd_kernel(const ga_mlp_bwd_desc d) {
     constexpr int KS1 = C / 32, KS2 = HC / 32, TN1 = HC / 32, TN2 = C / 32;
     constexpr int XS = KS1 * BM * 64, WS = KS1 * HC * 64, TS = KS2 * BM * 64;
     constexpr int NPC = HC * C / 8, NI = (NPC + 511) / 512;     // 16-byte pieces per weight chunk / per thread
+    constexpr int NCH = 4 * C / HC;                             // chunks of the hidden dimension (H = 4C)
+    static_assert(!WG || (HC == 64 && C == 96), "the in-kernel weight gradient is laid out for 4 x 6 tiles over 8 waves");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* Xs = smem;
     unsigned char* Ds = Xs + XS;
@@ -290,7 +326,6 @@ __global__ __launch_bounds__(512, 1) void mlp_bwd_kernel(const ga_mlp_bwd_desc d
     unsigned char* A2s = DHs + TS;
     float* B1s = reinterpret_cast<float*>(A2s + TS);               // [4C]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1, g = lane >> 4;
-    const long m0 = (long)blockIdx.x * BM;
     const bf16_t* W1 = reinterpret_cast<const bf16_t*>(d.W1);
     const bf16_t* W2T = reinterpret_cast<const bf16_t*>(d.W2T);
     const bf16_t* W1T = reinterpret_cast<const bf16_t*>(d.W1T);
@@ -328,114 +363,241 @@ __global__ __launch_bounds__(512, 1) void mlp_bwd_kernel(const ga_mlp_bwd_desc d
         }
     };
 
-    w_load(0);
-    stage_rows<BM, KS1, 512>(Xs, reinterpret_cast<const bf16_t*>(d.X), d.ldx, m0, d.M);
-    stage_rows<BM, KS1, 512>(Ds, reinterpret_cast<const bf16_t*>(d.DY), d.lddy, m0, d.M);
+    // WG: this wave's share of the weight gradient, kept through every tile the workgroup walks
+    constexpr int NDW = WG ? NCH : 1;
+    f32x4_t dw[NDW][3];
+    float bsum[NDW];
+    unsigned tra[2];                           // lane part of the transposed fragment read addresses, per 4-row half
+    if constexpr (WG) {
+#pragma unroll
+        for (int i = 0; i < NDW; ++i) {
+            bsum[i] = 0.f;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) dw[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        }
+        tra[0] = tr_off(lane, 0, 0);
+        tra[1] = tr_off(lane, 1, 0);
+    }
+    // wave-uniform part: slab and first unit of a 16-column block; units 2, 3 are units 0, 1 with address bit 5 flipped
+    const int wu = __builtin_amdgcn_readfirstlane(wave);
+    auto tr_blk = [&](const unsigned char* img, int blk, int ks) __attribute__((always_inline)) {
+        const unsigned o = (unsigned)(img - smem) + (blk >> 1) * BM * 64 + ks * 2048, x = (blk & 1) << 5;
+        return tr_frag(smem + ((tra[0] ^ x) + o), smem + ((tra[1] ^ x) + o));
+    };
+
     for (int i = tid; i < 4 * C; i += 512) B1s[i] = d.b1[i];
-    w12_store();
-    w3_store();
-    __syncthreads();
+    const long ntiles = (d.M + BM - 1) / BM;
+    long tile = blockIdx.x;
+    w_load(0);
+    while (true) {
+        const long m0 = tile * BM;
+        const bool first = !WG || tile == (long)blockIdx.x;
+        const bool next_tile = WG && tile + (long)gridDim.x < ntiles;
+        // WG: the per-tile addressing (row staging, DX rows) is derived from a copy of the thread index that the compiler cannot
+        // see through, so it is re-computed per tile and not kept -- spilled -- across the whole tile walk
+        int ttid = tid;
+        if constexpr (WG) asm volatile("" : "+v"(ttid));
+        stage_rows<BM, KS1, 512>(Xs, reinterpret_cast<const bf16_t*>(d.X), d.ldx, m0, d.M, ttid);
+        stage_rows<BM, KS1, 512>(Ds, reinterpret_cast<const bf16_t*>(d.DY), d.lddy, m0, d.M, ttid);
+        if (first) {                           // later tiles: chunk 0 of the weights was staged by the previous tile's last chunk
+            w12_store();
+            w3_store();
+        }
+        __syncthreads();
 
-    f32x4_t dx[TN2][2];
+        f32x4_t dx[TN2][2];
 #pragma unroll
-    for (int i = 0; i < TN2; ++i)
+        for (int i = 0; i < TN2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) dx[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < 2; ++j) dx[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-    for (int j0 = 0; j0 < d.H; j0 += HC) {
-        const bool more = j0 + HC < d.H;
-        if (more) w_load(j0 + HC);
-        // ---- P1
-        f32x4_t h[TN1][2], t[TN1][2];
+        // one chunk of HC hidden columns; `more`: stage the weights of chunk jn behind it
+        // this wave's 3 tiles of dW1 rows [j0 + 16 jt, + 16) from the chunk's DHs and the tile's Xs.  Rows = hidden (first
+        // operand), columns = channels; every lane takes part in every read (the transposing read needs EXEC all ones), only
+        // the bias dot is wave-conditional
+        auto wg_chunk = [&](f32x4_t (&dwc)[3], float& bs) __attribute__((always_inline)) {
+            typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+            const bf16x2_t ones2 = {(__bf16)1.0f, (__bf16)1.0f};
 #pragma unroll
-        for (int i = 0; i < TN1; ++i)
+            for (int ks = 0; ks < BM / 32; ++ks) {
+                const bf16x8_t hf8 = tr_blk(DHs, wu >> 1, ks);
 #pragma unroll
-            for (int j = 0; j < 2; ++j) h[i][j] = t[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+                for (int tc = 0; tc < 3; ++tc) {
+                    const bf16x8_t xf8 = tr_blk(Xs, 3 * (wu & 1) + tc, ks);
+                    dwc[tc] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hf8, xf8, dwc[tc], 0, 0, 0);
+                }
+                if ((wu & 1) == 0) {
 #pragma unroll
-        for (int ks = 0; ks < KS1; ++ks) {
-            bf16x8_t xf[2], df[2];
+                    for (int j = 0; j < 4; ++j)
+                        bs = __builtin_amdgcn_fdot2_f32_bf16(bf16x2_t{hf8[2 * j], hf8[2 * j + 1]}, ones2, bs, false);
+                }
+            }
+        };
+        auto chunk = [&](const int j0, const bool more, const int jn) __attribute__((always_inline)) {
+            if (more) w_load(jn);
+            // ---- P1
+            f32x4_t h[TN1][2], t[TN1][2];
 #pragma unroll
-            for (int tm = 0; tm < 2; ++tm) {
-                xf[tm] = frag(Xs + ks * BM * 64, wm * 32 + 16 * tm, lane);
-                df[tm] = frag(Ds + ks * BM * 64, wm * 32 + 16 * tm, lane);
+            for (int i = 0; i < TN1; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) h[i][j] = t[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < KS1; ++ks) {
+                bf16x8_t xf[2], df[2];
+#pragma unroll
+                for (int tm = 0; tm < 2; ++tm) {
+                    xf[tm] = frag(Xs + ks * BM * 64, wm * 32 + 16 * tm, lane);
+                    df[tm] = frag(Ds + ks * BM * 64, wm * 32 + 16 * tm, lane);
+                }
+#pragma unroll
+                for (int tn = 0; tn < TN1; ++tn) {
+                    const bf16x8_t w1f = frag(W1s + ks * HC * 64, wn * (HC / 2) + 16 * tn, lane);
+                    const bf16x8_t w2f = frag(W2Ts + ks * HC * 64, wn * (HC / 2) + 16 * tn, lane);
+#pragma unroll
+                    for (int tm = 0; tm < 2; ++tm) {
+                        h[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1f, xf[tm], h[tn][tm], 0, 0, 0);
+                        t[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2f, df[tm], t[tn][tm], 0, 0, 0);
+                    }
+                }
             }
 #pragma unroll
             for (int tn = 0; tn < TN1; ++tn) {
-                const bf16x8_t w1f = frag(W1s + ks * HC * 64, wn * (HC / 2) + 16 * tn, lane);
-                const bf16x8_t w2f = frag(W2Ts + ks * HC * 64, wn * (HC / 2) + 16 * tn, lane);
+                const int nl = wn * (HC / 2) + 16 * tn + 4 * g;
+                const float4 b = *reinterpret_cast<const float4*>(B1s + j0 + nl);
+                const float bb[4] = {b.x, b.y, b.z, b.w};
 #pragma unroll
                 for (int tm = 0; tm < 2; ++tm) {
-                    h[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1f, xf[tm], h[tn][tm], 0, 0, 0);
-                    t[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2f, df[tm], t[tn][tm], 0, 0, 0);
+                    float a[4], dh[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float gr;
+                        gelu_both_fast(h[tn][tm][r] + bb[r], a[r], gr);
+                        dh[r] = t[tn][tm][r] * gr;
+                    }
+                    const int row = wm * 32 + 16 * tm + (lane & 15);
+                    const unsigned o = (nl >> 5) * BM * 64 + slab_off(row, (nl & 31) >> 3) + (nl & 7) * 2;
+                    uint2 p;
+                    p.x = pack2bf(a[0], a[1]);
+                    p.y = pack2bf(a[2], a[3]);
+                    *reinterpret_cast<uint2*>(A2s + o) = p;
+                    p.x = pack2bf(dh[0], dh[1]);
+                    p.y = pack2bf(dh[2], dh[3]);
+                    *reinterpret_cast<uint2*>(DHs + o) = p;
                 }
             }
-        }
+            lds_barrier();                       // A2s / DHs complete; W1s / W2Ts are free
+            // ---- P2
 #pragma unroll
-        for (int tn = 0; tn < TN1; ++tn) {
-            const int nl = wn * (HC / 2) + 16 * tn + 4 * g;
-            const float4 b = *reinterpret_cast<const float4*>(B1s + j0 + nl);
-            const float bb[4] = {b.x, b.y, b.z, b.w};
+            for (int ks = 0; ks < KS2; ++ks) {
+                bf16x8_t af[2];
 #pragma unroll
-            for (int tm = 0; tm < 2; ++tm) {
-                float a[4], dh[4];
+                for (int tm = 0; tm < 2; ++tm) af[tm] = frag(DHs + ks * BM * 64, wm * 32 + 16 * tm, lane);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float gr;
-                    gelu_both_fast(h[tn][tm][r] + bb[r], a[r], gr);
-                    dh[r] = t[tn][tm][r] * gr;
-                }
-                const int row = wm * 32 + 16 * tm + (lane & 15);
-                const unsigned o = (nl >> 5) * BM * 64 + slab_off(row, (nl & 31) >> 3) + (nl & 7) * 2;
-                uint2 p;
-                p.x = pack2bf(a[0], a[1]);
-                p.y = pack2bf(a[2], a[3]);
-                *reinterpret_cast<uint2*>(A2s + o) = p;
-                p.x = pack2bf(dh[0], dh[1]);
-                p.y = pack2bf(dh[2], dh[3]);
-                *reinterpret_cast<uint2*>(DHs + o) = p;
-            }
-        }
-        lds_barrier();                       // A2s / DHs complete; W1s / W2Ts are free
-        // ---- P2
+                for (int tn = 0; tn < TN2; ++tn) {
+                    const bf16x8_t wf = frag(W1Ts + ks * C * 64, wn * (C / 2) + 16 * tn, lane);
 #pragma unroll
-        for (int ks = 0; ks < KS2; ++ks) {
-            bf16x8_t af[2];
-#pragma unroll
-            for (int tm = 0; tm < 2; ++tm) af[tm] = frag(DHs + ks * BM * 64, wm * 32 + 16 * tm, lane);
-#pragma unroll
-            for (int tn = 0; tn < TN2; ++tn) {
-                const bf16x8_t wf = frag(W1Ts + ks * C * 64, wn * (C / 2) + 16 * tn, lane);
-#pragma unroll
-                for (int tm = 0; tm < 2; ++tm) dx[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, af[tm], dx[tn][tm], 0, 0, 0);
-            }
-        }
-        // rows of a / dh of this chunk -> global (HC bf16 = HC/8 16-byte pieces per row)
-        {
-            constexpr int PPR = HC / 8, NP = BM * PPR / 512;
-            static_assert(BM * PPR % 512 == 0, "chunk rows must split evenly");
-#pragma unroll
-            for (int i = 0; i < NP; ++i) {
-                const int idx = tid + 512 * i;
-                const int r = idx / PPR, c = idx - r * PPR;
-                const long m = m0 + r;
-                if (m < d.M) {
-                    const unsigned o = (c >> 2) * BM * 64 + slab_off(r, c & 3);
-                    store16_nt(Aout + m * d.lda + j0 + c * 8, *reinterpret_cast<const uint4*>(A2s + o));
-                    store16_nt(DHout + m * d.lddh + j0 + c * 8, *reinterpret_cast<const uint4*>(DHs + o));
+                    for (int tm = 0; tm < 2; ++tm) dx[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, af[tm], dx[tn][tm], 0, 0, 0);
                 }
             }
+            if constexpr (WG) {
+                // the chunk loop stays rolled (unrolled, its six copies of the weight addressing spill); the accumulator set of
+                // the chunk is chosen by a scalar branch so that every register index is static
+                static_assert(NDW == 1 || NDW == 6, "one case per chunk");
+                switch (j0 / HC) {
+                    case 0: wg_chunk(dw[0], bsum[0]); break;
+                    case 1: wg_chunk(dw[1 % NDW], bsum[1 % NDW]); break;
+                    case 2: wg_chunk(dw[2 % NDW], bsum[2 % NDW]); break;
+                    case 3: wg_chunk(dw[3 % NDW], bsum[3 % NDW]); break;
+                    case 4: wg_chunk(dw[4 % NDW], bsum[4 % NDW]); break;
+                    default: wg_chunk(dw[5 % NDW], bsum[5 % NDW]); break;
+                }
+            }
+            // rows of a / dh of this chunk -> global (HC bf16 = HC/8 16-byte pieces per row)
+            if (Aout || DHout) {
+                constexpr int PPR = HC / 8, NP = BM * PPR / 512;
+                static_assert(BM * PPR % 512 == 0, "chunk rows must split evenly");
+                int ctid = tid;                  // WG: as ttid above -- no running row pointers across chunks and tiles
+                if constexpr (WG) asm volatile("" : "+v"(ctid));
+#pragma unroll
+                for (int i = 0; i < NP; ++i) {
+                    const int idx = ctid + 512 * i;
+                    const int r = idx / PPR, c = idx - r * PPR;
+                    const long m = m0 + r;
+                    if (m < d.M) {
+                        const unsigned o = (c >> 2) * BM * 64 + slab_off(r, c & 3);
+                        if (Aout) store16_nt(Aout + m * d.lda + j0 + c * 8, *reinterpret_cast<const uint4*>(A2s + o));
+                        if (DHout) store16_nt(DHout + m * d.lddh + j0 + c * 8, *reinterpret_cast<const uint4*>(DHs + o));
+                    }
+                }
+            }
+            if (more) w12_store();
+            lds_barrier();                       // A2s / DHs / W1Ts are free, the new W1s / W2Ts visible
+            if (more) w3_store();
+        };
+        for (int j0 = 0; j0 < d.H; j0 += HC) {
+            const bool last = j0 + HC >= d.H;
+            chunk(j0, !last || next_tile, last ? 0 : j0 + HC);
         }
-        if (more) w12_store();
-        lds_barrier();                       // A2s / DHs / W1Ts are free, the new W1s / W2Ts visible
-        if (more) w3_store();
+        u32x4_t nopre[BM / 64][RowPre<C, 512>::NR];
+#pragma unroll
+        for (int i = 0; i < BM / 64; ++i)
+#pragma unroll
+            for (int j = 0; j < RowPre<C, 512>::NR; ++j) nopre[i][j] = u32x4_t{0, 0, 0, 0};
+        // (the staging piece covers Xs and the head of Ds only: the weights staged for the next tile are beyond it)
+        int stid = tid;
+        if constexpr (WG) asm volatile("" : "+v"(stid));
+        store_rows<C, 512, 4, 2>(reinterpret_cast<float*>(smem), dx, stid >> 7, (stid >> 6) & 1, stid & 63, m0, d.M, nullptr, nullptr, 1,
+                                 false, nopre, reinterpret_cast<bf16_t*>(d.DX), d.lddx, stid);
+        if (!next_tile) break;
+        tile += gridDim.x;
+        __syncthreads();                         // the staging piece has been read: Xs / Ds may be staged again
     }
-    u32x4_t nopre[BM / 64][RowPre<C, 512>::NR];
+    if constexpr (WG) {
+        // lane: channel = column (lane & 15) of the tile, hidden rows 4 g + r
+        float* P = d.partials + (long)blockIdx.x * (4 * C * C + 4 * C);
+        int etid = tid;
+        asm volatile("" : "+v"(etid));
+        const int lane = etid & 63, g = lane >> 4, jt = wu >> 1;
 #pragma unroll
-    for (int i = 0; i < BM / 64; ++i)
+        for (int ch = 0; ch < NCH; ++ch) {
 #pragma unroll
-        for (int j = 0; j < RowPre<C, 512>::NR; ++j) nopre[i][j] = u32x4_t{0, 0, 0, 0};
-    store_rows<C, 512, 4, 2>(reinterpret_cast<float*>(smem), dx, wm, wn, lane, m0, d.M, nullptr, nullptr, 1, false, nopre,
-                             reinterpret_cast<bf16_t*>(d.DX), d.lddx);
+            for (int tc = 0; tc < 3; ++tc)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    P[(ch * HC + 16 * jt + 4 * g + r) * C + 16 * (3 * (wu & 1) + tc) + (lane & 15)] = dw[ch][tc][r];
+            float v = bsum[ch];                  // hidden column (lane & 15); the 4 lane groups hold row subsets
+            v += __shfl_xor(v, 16, 64);
+            v += __shfl_xor(v, 32, 64);
+            if ((wu & 1) == 0 && lane < 16) P[4 * C * C + ch * HC + 16 * jt + lane] = v;
+        }
+    }
+}
+
+// dW1[j][c] += sum_b part[b][j * C + c],  db1[j] += sum_b part[b][H * C + j], b in workgroup order whatever the grid: thread
+// group q of 4 sums the partials q, q + 4, ..., then the four sums are added in order.  n = H*C + H, a multiple of 4, as is C.
+__global__ __launch_bounds__(256) void mlp_bwd_wg_reduce_kernel(const float* __restrict__ part, int nparts, int n, int nw, int C,
+                                                                float* __restrict__ dW1, long ldw, float* __restrict__ db1) {
+    __shared__ float4 sh[3][64];
+    const int q = threadIdx.x >> 6;
+    const long i = ((long)blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (i < n) {
+#pragma unroll 4
+        for (int s = q; s < nparts; s += 4) {
+            const float4 b = *reinterpret_cast<const float4*>(part + (long)s * n + i);
+            a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+        }
+    }
+    if (q) sh[q - 1][threadIdx.x & 63] = a;
+    __syncthreads();
+    if (q || i >= n) return;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        const float4 b = sh[s][threadIdx.x];
+        a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+    }
+    float* dst = i < nw ? dW1 + (i / C) * ldw + (i % C) : db1 + (i - nw);
+    dst[0] += a.x; dst[1] += a.y; dst[2] += a.z; dst[3] += a.w;
 }
 
 template <int C, int HC> constexpr int bwd_lds() {
@@ -476,27 +638,82 @@ extern "C" int ga_mlp_fwd(const ga_mlp_desc* d, ga_stream_t stream) {
     return ga_check_launch("ga_mlp_fwd");
 }
 
+extern "C" int ga_mlp_bwd_wgrad_supported(int C, int H, int dtype) { return dtype == GA_BF16 && C == 96 && H == 4 * C; }
+
+namespace {
+
+int num_cus() {
+    static int n = [] {
+        int c = 256;
+        ga_device_info(&c, nullptr, nullptr);
+        return c;
+    }();
+    return n;
+}
+
+// persistent grid of the weight-gradient form: the workgroups that are resident at once (occupancy query, as the ring GEMM
+// does it), at most max_blocks when that is given, and never more than there are tiles -- so no workgroup is without a tile
+// and every partial is written.  0: the LDS cannot be reserved.
+int wg_grid(const ga_mlp_bwd_desc* d) {
+    constexpr int lds = bwd_lds<96, 64>();
+    static const int resident = [] {
+        auto kern = mlp_bwd_kernel<96, 64, true>;
+        if (!set_lds(kern, lds)) return 0;
+        int n = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, 512, lds) != hipSuccess || n < 1) n = 1;
+        return n * num_cus();
+    }();
+    long grid = resident;
+    if (d->max_blocks > 0) grid = std::min<long>(grid, d->max_blocks);
+    return (int)std::min<long>(grid, (d->M + BM - 1) / BM);
+}
+
+}  // namespace
+
+extern "C" size_t ga_mlp_bwd_partials(const ga_mlp_bwd_desc* d) {
+    if (!d || d->M <= 0 || !ga_mlp_bwd_wgrad_supported(d->C, d->H, d->dtype)) return 0;
+    return (size_t)wg_grid(d) * ((size_t)d->H * d->C + d->H) * sizeof(float);
+}
+
 extern "C" int ga_mlp_bwd(const ga_mlp_bwd_desc* d, ga_stream_t stream) {
-    GA_REQUIRE(d && d->X && d->DY && d->W1 && d->b1 && d->W2T && d->W1T && d->A && d->DH && d->DX && d->M > 0,
-               "ga_mlp_bwd: null / empty descriptor");
+    GA_REQUIRE(d && d->X && d->DY && d->W1 && d->b1 && d->W2T && d->W1T && d->DX && d->M > 0, "ga_mlp_bwd: null / empty descriptor");
     GA_REQUIRE(ga_mlp_supported(d->C, d->H, d->dtype), "ga_mlp_bwd: C=%d H=%d dtype=%d has no fused form (ga_mlp_supported)", d->C,
                d->H, d->dtype);
     GA_REQUIRE(aligned16(d->X) && aligned16(d->DY) && aligned16(d->W1) && aligned16(d->W2T) && aligned16(d->W1T) &&
                    aligned16(d->A) && aligned16(d->DH) && aligned16(d->DX) && aligned16(d->b1) && d->ldx % 8 == 0 &&
-                   d->lddy % 8 == 0 && d->ldw1 % 8 == 0 && d->ldw2t % 8 == 0 && d->ldw1t % 8 == 0 && d->lda % 8 == 0 &&
-                   d->lddh % 8 == 0 && d->lddx % 8 == 0 && d->ldx >= d->C && d->lddy >= d->C && d->ldw1 >= d->C &&
-                   d->ldw2t >= d->C && d->ldw1t >= d->H && d->lda >= d->H && d->lddh >= d->H && d->lddx >= d->C,
+                   d->lddy % 8 == 0 && d->ldw1 % 8 == 0 && d->ldw2t % 8 == 0 && d->ldw1t % 8 == 0 && (!d->A || d->lda % 8 == 0) &&
+                   (!d->DH || d->lddh % 8 == 0) && d->lddx % 8 == 0 && d->ldx >= d->C && d->lddy >= d->C && d->ldw1 >= d->C &&
+                   d->ldw2t >= d->C && d->ldw1t >= d->H && (!d->A || d->lda >= d->H) && (!d->DH || d->lddh >= d->H) &&
+                   d->lddx >= d->C,
                "ga_mlp_bwd: operands must be 16-byte aligned with leading dimensions in multiples of 8");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (d->dW1) {
+        // fc1 weight gradient accumulated in the kernel (persistent launch) + the fixed-order sum of the workgroups' partials
+        GA_REQUIRE(ga_mlp_bwd_wgrad_supported(d->C, d->H, d->dtype),
+                   "ga_mlp_bwd: dW1 is accumulated in the kernel at C=96 only, not C=%d H=%d dtype=%d (ga_mlp_bwd_wgrad_supported)",
+                   d->C, d->H, d->dtype);
+        GA_REQUIRE(d->db1 && d->partials && aligned16(d->partials) && d->ldw >= d->C && d->max_blocks >= 0,
+                   "ga_mlp_bwd: dW1 needs db1, 16-byte aligned partials and ldw >= C");
+        constexpr int lds = bwd_lds<96, 64>();
+        const int grid = wg_grid(d);
+        GA_REQUIRE(grid > 0, "ga_mlp_bwd: LDS");
+        const int n = d->H * d->C + d->H;
+        GA_REQUIRE(d->partials_bytes >= (size_t)grid * n * sizeof(float), "ga_mlp_bwd: partials holds %zu bytes, %zu needed (ga_mlp_bwd_partials)",
+                   (size_t)d->partials_bytes, (size_t)grid * n * sizeof(float));
+        hipLaunchKernelGGL((mlp_bwd_kernel<96, 64, true>), dim3(grid), dim3(512), lds, s, *d);
+        hipLaunchKernelGGL(mlp_bwd_wg_reduce_kernel, dim3((n / 4 + 63) / 64), dim3(256), 0, s, d->partials, grid, n, d->H * d->C, d->C,
+                           d->dW1, (long)d->ldw, d->db1);
+        return ga_check_launch("ga_mlp_bwd");
+    }
     const unsigned grid = (unsigned)((d->M + BM - 1) / BM);
     if (d->C == 96) {
         constexpr int lds = bwd_lds<96, 64>();
-        GA_REQUIRE(set_lds(mlp_bwd_kernel<96, 64>, lds), "ga_mlp_bwd: LDS");
-        hipLaunchKernelGGL((mlp_bwd_kernel<96, 64>), dim3(grid), dim3(512), lds, s, *d);
+        GA_REQUIRE(set_lds(mlp_bwd_kernel<96, 64, false>, lds), "ga_mlp_bwd: LDS");
+        hipLaunchKernelGGL((mlp_bwd_kernel<96, 64, false>), dim3(grid), dim3(512), lds, s, *d);
     } else {
         constexpr int lds = bwd_lds<192, 32>();
-        GA_REQUIRE(set_lds(mlp_bwd_kernel<192, 32>, lds), "ga_mlp_bwd: LDS");
-        hipLaunchKernelGGL((mlp_bwd_kernel<192, 32>), dim3(grid), dim3(512), lds, s, *d);
+        GA_REQUIRE(set_lds(mlp_bwd_kernel<192, 32, false>, lds), "ga_mlp_bwd: LDS");
+        hipLaunchKernelGGL((mlp_bwd_kernel<192, 32, false>), dim3(grid), dim3(512), lds, s, *d);
     }
     return ga_check_launch("ga_mlp_bwd");
 }

@@ -69,6 +69,7 @@ class GAEngine:
         self.tmps = {}
         # trunk weight-gradient launches on the backward plan's asynchronous lane (GAEXT_ASYNC_WGRAD=0: in line)
         self.async_wgrad = os.environ.get('GAEXT_ASYNC_WGRAD', '1') != '0'
+        self.mlp_wg1 = os.environ.get('GAEXT_MLP_WG1', '1') != '0'     # fc1 weight gradient inside the fused MLP backward (C = 96)
         self.fwd_split = max(1, int(os.environ.get('GAEXT_FWD_SPLIT', '2')))
         self.par_branch = os.environ.get('GAEXT_PAR_BRANCH', '1') != '0'   # stage-4 shortcut branch beside the main branch (forward)
         self.fwd_skew = int(os.environ.get('GAEXT_FWD_SKEW', '-1'))   # chain k+1 starts when chain k has passed this stage
@@ -608,13 +609,26 @@ class GAEngine:
         wl = ASYNC_LANE if side else Bk.lane
         ml = Bk.lane
         G2, gb2 = self.gbuf((C, 4 * C)), self.gbuf((C,))
-        dh = self.tmp('dh' + par, (M, 4 * C))
         gb1 = self.gbuf((4 * C,))
         G1 = self.gbuf((4 * C, C))
         g = self.tmp('g', (M, C))
-        if b['fused']:
+        if b['fused'] and self.mlp_wg1 and ops.mlp_bwd_wgrad_supported(C, 4 * C, dt):
+            # as below, and the fc1 weight gradient (G1, gb1) is accumulated by the same kernel from the dh / xn tiles it holds in
+            # LDS: dh is neither stored nor read back and the wg1 launch is gone (csrc/mlp.hip).  The workgroups' fp32 partials
+            # are written by the kernel and summed into G1 / gb1 by the reduce launch that the same call puts right behind it on
+            # this chain lane; the next block's mlp_bwd, later on the same lane, writes them again -- nothing on another lane
+            # ever reads them (the parity suffix follows dh / du all the same)
+            a = self.tmp('a' + par, (M, 4 * C))
+            part = self.tmp('mlpwg' + par, (ops.mlp_bwd_partials(M, C, dt) // 4,), torch.float32)
+            Bk.mlp_bwd(b['xn'], dyz, W[pre + self.NAMES['fc1'] + 'weight'], W[pre + 'b1e'], W[pre + self.NAMES['fc2'] + 'weight.T'],
+                       W[pre + self.NAMES['fc1'] + 'weight.T'], a, None, g, M, C, dt, dW1=G1, db1=gb1, partials=part, label=pre + 'mlpb')
+            Bk.lane = wl
+            Bk.wgrad(dyz, a, G2, M, C, 4 * C, dt, dbias=gb2, label=pre + 'wg2')
+            Bk.lane = ml
+        elif b['fused']:
             # hidden pre-activation re-computed; a / dh written once for the two weight-gradient GEMMs, dh stays on chip for dgrad1
             a = self.tmp('a' + par, (M, 4 * C))
+            dh = self.tmp('dh' + par, (M, 4 * C))
             Bk.mlp_bwd(b['xn'], dyz, W[pre + self.NAMES['fc1'] + 'weight'], W[pre + 'b1e'], W[pre + self.NAMES['fc2'] + 'weight.T'],
                        W[pre + self.NAMES['fc1'] + 'weight.T'], a, dh, g, M, C, dt, label=pre + 'mlpb')
             Bk.lane = wl
@@ -622,6 +636,7 @@ class GAEngine:
             Bk.wgrad(dh, b['xn'], G1, M, 4 * C, C, dt, dbias=gb1, label=pre + 'wg1')
             Bk.lane = ml
         else:
+            dh = self.tmp('dh' + par, (M, 4 * C))
             Bk.lane = wl
             Bk.wgrad(dyz, b['a'], G2, M, C, 4 * C, dt, dbias=gb2, label=pre + 'wg2')
             Bk.lane = ml

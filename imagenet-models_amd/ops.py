@@ -448,8 +448,12 @@ class Plan:
         d.Y, d.ldy, d.M, d.C, d.H, d.dtype = _ptr(Y), Cdim, M, Cdim, H, dtype
         self._add('ga_mlp_fwd', (C.byref(d),), label, keep=(d, X, W1, b1, W2, b2, R, rowscale, Y))
 
-    def mlp_bwd(self, X, DY, W1, b1, W2T, W1T, A, DH, DX, M, Cdim, dtype, ldw1=None, ldw2t=None, ldw1t=None, label=None):
-        """fused dgrad2 -> dgrad1 with the hidden pre-activation re-computed: A = gelu(X W1^T + b1), DH = (DY W2) gelu'(.), DX = DH W1"""
+    def mlp_bwd(self, X, DY, W1, b1, W2T, W1T, A, DH, DX, M, Cdim, dtype, ldw1=None, ldw2t=None, ldw1t=None, label=None,
+                dW1=None, db1=None, partials=None, max_blocks=0):
+        """fused dgrad2 -> dgrad1 with the hidden pre-activation re-computed: A = gelu(X W1^T + b1), DH = (DY W2) gelu'(.), DX = DH W1.
+        A / DH = None: not stored.  dW1 (fp32 [4C, C], with db1 fp32 [4C]): the fc1 weight gradient DH^T X and the column sums of
+        DH are accumulated into them inside the kernel (C = 96: mlp_bwd_wgrad_supported); partials: fp32 scratch of
+        mlp_bwd_partials(...) bytes, free again once the call's work is done; max_blocks caps the persistent grid (0: automatic)"""
         d = L.MlpBwdDesc()
         H = 4 * Cdim
         d.X, d.ldx, d.DY, d.lddy = _ptr(X), Cdim, _ptr(DY), Cdim
@@ -457,7 +461,12 @@ class Plan:
         d.W2T, d.ldw2t, d.W1T, d.ldw1t = _ptr(W2T), (Cdim if ldw2t is None else ldw2t), _ptr(W1T), (H if ldw1t is None else ldw1t)
         d.A, d.lda, d.DH, d.lddh, d.DX, d.lddx = _ptr(A), H, _ptr(DH), H, _ptr(DX), Cdim
         d.M, d.C, d.H, d.dtype = M, Cdim, H, dtype
-        self._add('ga_mlp_bwd', (C.byref(d),), label, keep=(d, X, DY, W1, b1, W2T, W1T, A, DH, DX))
+        if dW1 is not None:
+            assert dW1.dtype == torch.float32 and db1 is not None and db1.dtype == torch.float32 and partials is not None
+            assert dW1.stride(-1) == 1 and partials.dtype == torch.float32 and partials.is_contiguous()
+            d.dW1, d.ldw, d.db1 = _ptr(dW1), dW1.stride(0), _ptr(db1)
+            d.partials, d.partials_bytes, d.max_blocks = _ptr(partials), partials.numel() * 4, max_blocks
+        self._add('ga_mlp_bwd', (C.byref(d),), label, keep=(d, X, DY, W1, b1, W2T, W1T, A, DH, DX, dW1, db1, partials))
 
     def wgrad(self, Y, X, dW, M, N, K, dtype, ldy=None, ldx=None, ldw=None, batch=1, strideY=0, strideX=0, strideW=0,
               x_kind=A_PLAIN, x_dims=(0, 0, 0), x_act=ACT_NONE, dbias=None, strideDbias=0, alpha=1.0, split_m=None,
@@ -952,6 +961,18 @@ class Plan:
 
 def mlp_supported(Cdim, H, dtype):
     return bool(L.load().ga_mlp_supported(Cdim, H, dtype))
+
+
+def mlp_bwd_wgrad_supported(Cdim, H, dtype):
+    """Plan.mlp_bwd can accumulate the fc1 weight gradient itself (dW1=...) at this shape"""
+    return bool(L.load().ga_mlp_bwd_wgrad_supported(Cdim, H, dtype))
+
+
+def mlp_bwd_partials(M, Cdim, dtype, max_blocks=0):
+    """bytes of the fp32 `partials` scratch Plan.mlp_bwd(dW1=...) takes for M rows (0: not supported)"""
+    d = L.MlpBwdDesc()
+    d.M, d.C, d.H, d.dtype, d.max_blocks = M, Cdim, 4 * Cdim, dtype, max_blocks
+    return int(L.load().ga_mlp_bwd_partials(C.byref(d)))
 
 
 def cswin_attn_bwd_workspace(d):

@@ -621,10 +621,26 @@ typedef struct {
     void* DH; int64_t lddh;
     void* DX; int64_t lddx;
     int64_t M; int C, H, dtype;
+    /* optional (all zero: the launch above).  dW1 given: the fc1 weight gradient is accumulated inside the kernel, from the DH
+     * and X tiles it holds on chip, so DH need not be stored for a ga_wgrad launch:
+     *   dW1 [H][ldw] fp32 += DH^T X,  db1 [H] fp32 += column sums of DH   (DH as rounded to bf16, fp32 accumulation)
+     * C = 96 only (ga_mlp_bwd_wgrad_supported; an error otherwise).  The launch is then persistent: each workgroup walks
+     * several 128-row tiles and leaves one fp32 partial [H*C + H] in `partials` (caller-owned scratch of ga_mlp_bwd_partials(d)
+     * bytes, 16-byte aligned, dead once the call's work is done); a second kernel adds the partials in a fixed order -- no
+     * float atomics, two runs give the same bits.  max_blocks: 0 = as many workgroups as are resident at once, else a cap. */
+    float* dW1; int64_t ldw;
+    float* db1;
+    float* partials; size_t partials_bytes;
+    int max_blocks;
 } ga_mlp_bwd_desc;
 int ga_mlp_supported(int C, int H, int dtype);
 int ga_mlp_fwd(const ga_mlp_desc* d, ga_stream_t stream);
+/* A / DH may each be NULL: that tensor is not stored */
 int ga_mlp_bwd(const ga_mlp_bwd_desc* d, ga_stream_t stream);
+int ga_mlp_bwd_wgrad_supported(int C, int H, int dtype);
+/* bytes of `partials` the descriptor's launch with dW1 needs (depends on M, max_blocks and the device; the pointers are not
+ * looked at); 0 where ga_mlp_bwd_wgrad_supported says no */
+size_t ga_mlp_bwd_partials(const ga_mlp_bwd_desc* d);
 
 /* Alignment-free forms for the odd-width variants (ga_convnext_*_688, base_976: 86 / 172 / 122 / 244 channels per group are off
  * the 16-byte grid of the MFMA kernels).  The heads' grouped 1x1 convolutions act on one token per image (rows = batch):

@@ -45,6 +45,23 @@ def main():
         for name, fn, k in (('fwd unfused', unfused_fwd, 1), ('fwd fused', fused_fwd, 1), ('bwd unfused', unfused_bwd, 1), ('bwd fused', fused_bwd, 1.5)):
             ms = timeit(fn)
             print(f'C={C} M={M} {name}: {ms:.3f} ms  ({gf * k / ms:.0f} TFLOP/s)', flush=True)
+        if not ops.mlp_bwd_wgrad_supported(C, H, gd):
+            continue
+        # backward with both weight gradients: mlp_bwd + wgrad(dh, xn) + wgrad(dyz, a) against mlp_bwd(dW1=...) + wgrad(dyz, a)
+        G1 = torch.zeros(H, C, device='cuda'); gb1 = torch.zeros(H, device='cuda')
+        G2 = torch.zeros(C, H, device='cuda'); gb2 = torch.zeros(C, device='cuda')
+        part = torch.empty(ops.mlp_bwd_partials(M, C, gd) // 4, device='cuda')
+        def bwd_wg_launches():
+            p.mlp_bwd(X, DY, W1, b1, W2T, W1T, a, dh, DX, M, C, gd)
+            p.wgrad(dh, X, G1, M, H, C, gd, dbias=gb1)
+            p.wgrad(DY, a, G2, M, C, H, gd, dbias=gb2)
+        def bwd_wg_fused():
+            p.mlp_bwd(X, DY, W1, b1, W2T, W1T, a, None, DX, M, C, gd, dW1=G1, db1=gb1, partials=part)
+            p.wgrad(DY, a, G2, M, C, H, gd, dbias=gb2)
+        def fused_only():
+            p.mlp_bwd(X, DY, W1, b1, W2T, W1T, a, None, DX, M, C, gd, dW1=G1, db1=gb1, partials=part)
+        for name, fn in (('bwd + wg1 + wg2 (three launches)', bwd_wg_launches), ('bwd(dW1) + wg2', bwd_wg_fused), ('bwd(dW1) alone', fused_only)):
+            print(f'C={C} M={M} {name}: {timeit(fn):.3f} ms', flush=True)
 
 
 if __name__ == '__main__':
