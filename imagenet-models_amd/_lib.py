@@ -205,6 +205,9 @@ _SIGS = {
     'ga_loss_dense_fwd_bwd': ([vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, f32, f32, f32, i32, vp], i32),
     'ga_u8_normalize': ([vp, vp, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp], i32),
     'ga_input_erase': ([vp, i32, vp, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, i32, i32, C.c_uint64, C.c_uint64, vp], i32),
+    'ga_input_collate': ([vp, i32, vp, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp, i32, i32, C.c_uint64, C.c_uint64, vp],
+                         i32),
+    'ga_mixup_target_elem': ([vp, vp, i32, i32, vp, C.c_double, vp], i32),
     'ga_mixup_batch': ([vp, vp, i32, i32, i32, i32, C.c_double, i32, i32, i32, i32, i32, vp], i32),
     'ga_mixup_target': ([vp, vp, i32, i32, C.c_double, C.c_double, vp], i32),
     'ga_agc_clip': ([vp, vp, vp, i32, f32, f32, vp], i32),

@@ -4,18 +4,30 @@ on).  lam and the cut box are drawn on the host from numpy's generator exactly a
 the dense smoothed target are HIP kernels (ga_mixup_batch, ga_mixup_target).  The dense (B, num_classes) target goes to
 ga_loss / map_loss / TrainStep, which then evaluate SoftTargetCrossEntropy (or BinaryCrossEntropy) on it (train.py:616-621).
 
-Modes 'pair' and 'elem' of timm's Mixup are not built (GA/README's recipes use the default 'batch')."""
+Mixup is the --no-prefetcher order of the reference (mix the normalised fp32 batch on the device); no recipe runs it.  With the
+prefetcher on, which every recipe has (MAP/train.py:383), timm mixes at COLLATE time: FastCollateMixup blends the uint8 images
+and rounds every blended value back to uint8, PrefetchLoader normalises on the device, RandomErasing comes last on the mixed
+image.  FastCollateMixup below is that order as one HIP pass (ga_input_collate): a per-sample table {kind, box, lam, 1 - lam}
+drawn on the host, so timm's modes 'batch', 'elem' and 'pair' are the same kernel.  Given an fp32 batch it is timm's Mixup in
+those modes (no rounding to integers, no normalisation).  Mode 'half' halves the batch the engine was planned for: refused.
+
+timm is not vendored in the reference and not installed: the samplers restate its published algorithm, parity with timm itself
+is unpinned (as for oracle/mixup_oracle.py)."""
 import numpy as np
 import torch
 
 from . import ops
+
+KIND_NONE, KIND_MIXUP, KIND_CUTMIX = 0, 1, 2
+_STAGING = 4       # pinned host tables in flight, as random_erasing.py: a table is rewritten only after its copy of 4 calls ago
 
 
 class Mixup:
     def __init__(self, mixup_alpha=1.0, cutmix_alpha=0.0, cutmix_minmax=None, prob=1.0, switch_prob=0.5, mode='batch',
                  correct_lam=True, label_smoothing=0.1, num_classes=1000, rng=None):
         if mode != 'batch':
-            raise NotImplementedError(f"Mixup mode {mode!r}: only 'batch' is built")
+            raise NotImplementedError(f"Mixup mode {mode!r}: only 'batch' is built here; FastCollateMixup runs 'elem' and 'pair' "
+                                      '(on uint8 and on fp32 batches)')
         self.mixup_alpha, self.cutmix_alpha, self.cutmix_minmax = mixup_alpha, cutmix_alpha, cutmix_minmax
         if cutmix_minmax is not None:
             assert len(cutmix_minmax) == 2
@@ -85,3 +97,131 @@ class Mixup:
         p.mixup_target(target.contiguous(), dense, self.num_classes, lam, self.label_smoothing)
         self.last = (lam, use_cutmix, box)
         return out, dense
+
+
+class FastCollateMixup(Mixup):
+    """timm's FastCollateMixup + PrefetchLoader order on the device: mix the uint8 batch (rounded back to uint8), normalise,
+    erase -- one pass (ga_input_collate).  Same constructor as Mixup; mode 'batch' | 'elem' | 'pair'.  The partner of sample i
+    is B-1-i.  Parameters are drawn on the host from self.rng in timm's order (sample())."""
+
+    def __init__(self, mixup_alpha=1.0, cutmix_alpha=0.0, cutmix_minmax=None, prob=1.0, switch_prob=0.5, mode='batch',
+                 correct_lam=True, label_smoothing=0.1, num_classes=1000, rng=None):
+        if mode == 'half':
+            raise ValueError("FastCollateMixup mode 'half' returns half of the batch: the engine is planned for the full batch size, "
+                             "so it is not built ('batch', 'elem' or 'pair')")
+        if mode not in ('batch', 'elem', 'pair'):
+            raise ValueError(f"FastCollateMixup mode {mode!r}: 'batch', 'elem' or 'pair'")
+        super().__init__(mixup_alpha, cutmix_alpha, cutmix_minmax, prob, switch_prob, 'batch', correct_lam, label_smoothing,
+                         num_classes, rng)
+        self.mode = mode
+        self.last = None                     # the int32 (B, 8) table of the last call, for logging / tests
+        self._key, self._host, self._copied, self._dev, self._out, self._dense, self._calls = None, None, None, None, None, None, 0
+
+    def _params_per_elem(self, n):
+        lam = np.ones(n, dtype=np.float32)
+        use_cutmix = np.zeros(n, dtype=bool)
+        if self.mixup_enabled:
+            if self.mixup_alpha > 0.0 and self.cutmix_alpha > 0.0:
+                use_cutmix = self.rng.rand(n) < self.switch_prob
+                lam_mix = np.where(use_cutmix, self.rng.beta(self.cutmix_alpha, self.cutmix_alpha, size=n),
+                                   self.rng.beta(self.mixup_alpha, self.mixup_alpha, size=n))
+            elif self.mixup_alpha > 0.0:
+                lam_mix = self.rng.beta(self.mixup_alpha, self.mixup_alpha, size=n)
+            elif self.cutmix_alpha > 0.0:
+                use_cutmix = np.ones(n, dtype=bool)
+                lam_mix = self.rng.beta(self.cutmix_alpha, self.cutmix_alpha, size=n)
+            else:
+                raise AssertionError('one of mixup_alpha > 0, cutmix_alpha > 0, cutmix_minmax not None must be true')
+            lam = np.where(self.rng.rand(n) < self.mix_prob, lam_mix.astype(np.float32), lam)
+        return lam, use_cutmix
+
+    def _draw(self, B, H, W):
+        """-> (int32 (B, 8) table {kind, yl, yh, xl, xh, bits(l), bits(m), 0}, lam): lam is the python float of 'batch' mode (the
+        target kernel forms its complement in double) or the float32 (B,) vector of 'elem' / 'pair'"""
+        assert B % 2 == 0, 'Batch size should be even when using this'
+        tab = np.zeros((B, 8), dtype=np.int32)
+        lm = tab[:, 5:7].view(np.float32)                     # l, m as their bit patterns
+        if self.mode == 'batch':
+            lam, use_cutmix = self._params_per_batch()
+            if lam != 1.0:
+                if use_cutmix:
+                    box, lam = self._box(H, W, lam)
+                    tab[:, 0] = KIND_CUTMIX
+                    tab[:, 1:5] = box
+                else:
+                    tab[:, 0] = KIND_MIXUP
+            lm[:, 0] = np.float32(lam)
+            lm[:, 1] = np.float32(1.0 - lam)                  # numpy with a scalar lam: the complement in double, rounded once
+            return tab, lam
+        n = B if self.mode == 'elem' else B // 2
+        lam, use_cutmix = self._params_per_elem(n)
+        for i in range(n):
+            if lam[i] == 1.0:
+                continue
+            rows = (i,) if self.mode == 'elem' else (i, B - 1 - i)
+            if use_cutmix[i]:
+                box, lam[i] = self._box(H, W, lam[i])         # the corrected lam goes back into the float32 vector
+                for r in rows:
+                    tab[r, 0] = KIND_CUTMIX
+                    tab[r, 1:5] = box
+            else:
+                for r in rows:
+                    tab[r, 0] = KIND_MIXUP
+        if self.mode == 'pair':
+            lam = np.concatenate((lam, lam[::-1]))
+        lm[:, 0] = lam
+        lm[:, 1] = np.float32(1.0) - lam                      # numpy with a float32 lam vector: subtracted in fp32
+        return tab, lam
+
+    def sample(self, B, H, W):
+        """the per-sample mix table of one batch (host only): int32 (B, 8) rows {kind, yl, yh, xl, xh, bits(l), bits(m), 0};
+        `table[:, 5:7].view(np.float32)` are l and m"""
+        return self._draw(B, H, W)[0]
+
+    def _buffers(self, x):
+        B, C, H, W = x.shape
+        key = (tuple(x.shape), x.device, self.num_classes)
+        if self._key != key:
+            self._key = key
+            # one staging block per slot: the (B, 8) table and, behind it, the B lams of the target kernel
+            self._host = [torch.zeros(B * 9, dtype=torch.int32).pin_memory() for _ in range(_STAGING)]
+            self._copied = [None] * _STAGING
+            self._dev = torch.zeros(B * 9, dtype=torch.int32, device=x.device)
+            self._out = torch.empty(B, C, H, W, dtype=torch.float32, device=x.device)
+            self._dense = torch.empty(B, self.num_classes, dtype=torch.float32, device=x.device)
+
+    def __call__(self, x, target, random_erasing=None, mean=None, std=None):
+        """x: (B, C, H, W) uint8 on the device (mixed in uint8, then normalised with mean / std, 0..255 units) or fp32 (mixed as
+        it is); target: (B,) int64; random_erasing: an imagenet_models_amd.RandomErasing whose boxes are filled in the same
+        pass, on the mixed image -> (fp32 batch, dense target (B, num_classes)), both in buffers this object owns and reuses"""
+        if not x.is_cuda:
+            raise RuntimeError('FastCollateMixup runs on the HIP kernels only (no CPU fallback)')
+        if x.dtype not in (torch.uint8, torch.float32) or x.dim() != 4:
+            raise TypeError(f'FastCollateMixup expects a uint8 or float32 (B, C, H, W) batch, got {x.dtype} {tuple(x.shape)}')
+        if x.dtype == torch.uint8 and (mean is None or std is None):
+            raise ValueError('FastCollateMixup on a uint8 batch normalises it in the same pass: pass mean / std (0..255 units)')
+        B, _, H, W = x.shape
+        x = x.contiguous()
+        self._buffers(x)
+        tab, lam = self._draw(B, H, W)
+        slot = self._calls % _STAGING
+        if self._copied[slot] is not None:
+            self._copied[slot].synchronize()          # complete long ago in a running loop: no stall
+        host = self._host[slot].numpy()
+        host[:B * 8] = tab.reshape(-1)
+        host[B * 8:] = tab[:, 5]                       # bits(l): the fp32 lam[B] of ga_mixup_target_elem
+        self._dev.copy_(self._host[slot], non_blocking=True)
+        ev = self._copied[slot] or torch.cuda.Event()
+        ev.record()
+        self._copied[slot] = ev
+        p = ops.Plan(eager=True)
+        boxes, max_count, mode, seed, offset = random_erasing.stage(x) if random_erasing is not None else (None, 0, 0, 0, 0)
+        p.input_collate(x, self._out, self._dev[:B * 8], boxes, max_count, mode, seed, offset, mean, std)
+        target = target.contiguous()
+        if self.mode == 'batch':
+            p.mixup_target(target, self._dense, self.num_classes, lam, self.label_smoothing)
+        else:
+            p.mixup_target_elem(target, self._dense, self.num_classes, self._dev[B * 8:].view(torch.float32), self.label_smoothing)
+        self._calls += 1
+        self.last = tab
+        return self._out, self._dense

@@ -861,6 +861,23 @@ class Plan:
         self._add('ga_input_erase', (_ptr(x), int(u8), _ptr(out), B, CH, H, W, m, s, _ptr(boxes), int(max_count), int(mode),
                                      int(seed) & mask, int(offset) & mask), label, keep=(x, out, boxes, m, s))
 
+    def input_collate(self, x, out, mix, boxes=None, max_count=0, mode=0, seed=0, offset=0, mean=None, std=None, label=None):
+        """timm's collate-time order in one pass: per-sample mixup / cutmix of a uint8 batch (rounded back to uint8), the
+        normalisation, RandomErasing last.  mix = device int32 (B, 8) rows {kind, yl, yh, xl, xh, bits(l), bits(m), 0}; boxes /
+        max_count / mode / seed / offset as input_erase (boxes None: no erase).  An fp32 x is blended / box-copied as it is."""
+        B, CH, H, W = x.shape
+        u8 = x.dtype == torch.uint8
+        m = (C.c_float * CH)(*[float(v) for v in mean]) if u8 else None
+        s = (C.c_float * CH)(*[float(v) for v in std]) if u8 else None
+        mask = (1 << 64) - 1
+        self._add('ga_input_collate', (_ptr(x), int(u8), _ptr(out), B, CH, H, W, m, s, _ptr(mix), _ptr(boxes), int(max_count), int(mode),
+                                       int(seed) & mask, int(offset) & mask), label, keep=(x, out, mix, boxes, m, s))
+
+    def mixup_target_elem(self, target, out, NC, lam, smoothing, label=None):
+        """dense target of per-sample lams: lam = device fp32 (B,)"""
+        self._add('ga_mixup_target_elem', (_ptr(target), _ptr(out), target.numel(), NC, _ptr(lam), float(smoothing)), label,
+                  keep=(target, out, lam))
+
     def mixup_batch(self, x, out, lam, cutmix=False, box=(0, 0, 0, 0), label=None):
         B, CH, H, W = x.shape
         yl, yh, xl, xh = (int(v) for v in box)

@@ -60,24 +60,18 @@ class RandomErasing:
     def _buffers(self, x):
         B, C, H, W = x.shape
         key = (tuple(x.shape), x.device)
-        if self._out is None or self._key != key:
+        if self._host is None or self._key != key:
             self._key = key
             self._host = [torch.zeros(B, self.max_count, 4, dtype=torch.int32).pin_memory() for _ in range(_STAGING)]
             self._copied = [None] * _STAGING
             self._dev = torch.zeros(B, self.max_count, 4, dtype=torch.int32, device=x.device)
-            self._out = torch.empty(B, C, H, W, dtype=torch.float32, device=x.device)
+            self._out = None
 
-    def __call__(self, x, mean=None, std=None):
-        """x: (B, C, H, W) uint8 (normalised with mean / std, 0..255 units, in the same pass) or fp32 (copied) on the device
-        -> the erased fp32 batch, in a buffer this object owns and reuses; x itself is not modified"""
-        if not x.is_cuda:
-            raise RuntimeError('RandomErasing runs on the HIP kernels only (no CPU fallback)')
-        if x.dtype not in (torch.uint8, torch.float32) or x.dim() != 4:
-            raise TypeError(f'RandomErasing expects a uint8 or float32 (B, C, H, W) batch, got {x.dtype} {tuple(x.shape)}')
-        if x.dtype == torch.uint8 and (mean is None or std is None):
-            raise ValueError('RandomErasing on a uint8 batch normalises it in the same pass: pass mean / std (0..255 units)')
+    def stage(self, x):
+        """draw the boxes of one batch and stage their table on the device, for a launch the caller makes (the fused collate
+        pass, mixup.FastCollateMixup) -> (device int32 (B, max_count, 4) table, max_count, mode code, seed, offset of THIS call);
+        the offset is advanced: one per call, whoever launches"""
         B, _, H, W = x.shape
-        x = x.contiguous()
         self._buffers(x)
         boxes = self.sample(B, H, W)
         slot = self._calls % _STAGING
@@ -94,8 +88,24 @@ class RandomErasing:
         ev = self._copied[slot] or torch.cuda.Event()
         ev.record()
         self._copied[slot] = ev
-        ops.Plan(eager=True).input_erase(x, self._out, self._dev, self.max_count, _MODES[self.mode], self.seed, self.offset, mean, std)
+        offset = self.offset
         self.offset += 1
         self._calls += 1
         self.last_boxes = boxes
+        return self._dev, self.max_count, _MODES[self.mode], self.seed, offset
+
+    def __call__(self, x, mean=None, std=None):
+        """x: (B, C, H, W) uint8 (normalised with mean / std, 0..255 units, in the same pass) or fp32 (copied) on the device
+        -> the erased fp32 batch, in a buffer this object owns and reuses; x itself is not modified"""
+        if not x.is_cuda:
+            raise RuntimeError('RandomErasing runs on the HIP kernels only (no CPU fallback)')
+        if x.dtype not in (torch.uint8, torch.float32) or x.dim() != 4:
+            raise TypeError(f'RandomErasing expects a uint8 or float32 (B, C, H, W) batch, got {x.dtype} {tuple(x.shape)}')
+        if x.dtype == torch.uint8 and (mean is None or std is None):
+            raise ValueError('RandomErasing on a uint8 batch normalises it in the same pass: pass mean / std (0..255 units)')
+        x = x.contiguous()
+        dev, max_count, mode, seed, offset = self.stage(x)
+        if self._out is None:
+            self._out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        ops.Plan(eager=True).input_erase(x, self._out, dev, max_count, mode, seed, offset, mean, std)
         return self._out

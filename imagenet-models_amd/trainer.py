@@ -66,10 +66,19 @@ class TrainStep:
     def __init__(self, model, optimizer, batch, lam=0.0, loss='ce', smoothing=0.0, grad_accumulation=1,
                  process_group=None, clip_grad=None, clip_mode='norm', broadcast_buffers=True, bucket_elems=BUCKET_ELEMS,
                  mixup_fn=None, bce_target_thresh=None, comm=None, force_buckets=False, nan_guard=False,
-                 overlap_optimizer=False, random_erasing=None):
-        """random_erasing: an imagenet_models_amd.RandomErasing -- the input goes normalise -> erase -> mixup -> engine, the order
-        of the reference (timm's PrefetchLoader erases the normalised batch on the device, mixup_fn follows: MAP/train.py:643-646);
-        for a uint8 batch the erase pass IS the normalisation (ga_input_erase), so the batch is passed over once.
+                 overlap_optimizer=False, random_erasing=None, collate_mixup=None):
+        """The input stage has two orders.
+        Default (mixup_fn / random_erasing): normalise -> erase -> mixup -> engine, all in fp32.  random_erasing is an
+        imagenet_models_amd.RandomErasing (for a uint8 batch the erase pass IS the normalisation, ga_input_erase, so the batch is
+        passed over once), mixup_fn an imagenet_models_amd.Mixup (or a FastCollateMixup, which on an fp32 batch is timm's Mixup in
+        modes 'elem' / 'pair' as well).  This is timm's PrefetchLoader erase followed by the
+        --no-prefetcher mixup_fn (MAP/train.py:614-626,643-646): a combination timm itself never runs -- the erase boxes of both
+        partners are blended into each other and the mixture is never quantised.  It stays the default because every committed
+        number was taken with it.
+        collate_mixup (opt-in): an imagenet_models_amd.FastCollateMixup -- the order every reference recipe runs (prefetcher on,
+        MAP/train.py:383): mixup / cutmix on the uint8 batch at collate time, each blended value rounded back to uint8, then the
+        normalisation, then random_erasing LAST on the mixed image -- one HIP pass (ga_input_collate).  It needs a uint8 batch,
+        takes this step's random_erasing into the fused pass, and excludes mixup_fn.
         comm: an imagenet_models_amd.NativeComm -- the gradient buckets (and the BatchNorm-buffer broadcast) go through the
         library's own RCCL entry points (ga_allreduce_bucket on a side stream) instead of torch.distributed.
         force_buckets: take the segmented-backward + bucketed-reduction path even with one rank (tests: the real collective
@@ -77,12 +86,16 @@ class TrainStep:
         nan_guard: the device-side counterpart of MAP/train.py:887-891 (all_gather of the loss + isnan + exit): the loss value
         rides in the LAST gradient bucket's reduction as one extra element; `last_loss_sum` (a device tensor, the sum of the
         ranks' scaled losses) can be inspected by the caller at its logging interval -- no host synchronisation per step."""
+        if mixup_fn is not None and collate_mixup is not None:
+            raise ValueError('TrainStep: mixup_fn (mix the normalised fp32 batch) and collate_mixup (mix the uint8 batch at collate '
+                             'time) are two orders of the same augmentation: pass one of them')
         self.model, self.opt = model, optimizer
         self.eng = model.engine(batch, True)
         self.lam, self.kind, self.smoothing = lam, _KINDS[loss], smoothing
         # mixup / cutmix (imagenet_models_amd.Mixup, GA/train.py:727-728): applied to every batch, the loss then runs on the
         # dense target it returns (SoftTargetCrossEntropy / BinaryCrossEntropy, train.py:616-621)
         self.mixup_fn = mixup_fn
+        self.collate_mixup = collate_mixup
         self.random_erasing = random_erasing
         self.bce_threshold = -1.0 if bce_target_thresh is None else float(bce_target_thresh)
         self.accum = grad_accumulation
@@ -186,7 +199,11 @@ class TrainStep:
                 dist.broadcast(self.flat_buffers, 0, group=self.pg)
         # the reference divides the loss by grad_accumulation (train.py:750); DDP averages over ranks
         scale = 1.0 / (self.accum * self.world)
-        if self.random_erasing is not None:
+        if self.collate_mixup is not None:
+            if x.dtype != torch.uint8:
+                raise TypeError(f'TrainStep(collate_mixup=...) mixes the uint8 batch of the loader, got {x.dtype}')
+            x, target = self.collate_mixup(x, target, self.random_erasing, *eng.input_stats())
+        elif self.random_erasing is not None:
             x = self.random_erasing(x, *eng.input_stats())
         if self.mixup_fn is not None:
             # a uint8 batch (PrefetchLoader layout) is normalised on the device FIRST: Mixup blends normalised pixels, and a

@@ -574,6 +574,29 @@ int ga_u8_normalize(const void* x, float* out, int B, int CH, int H, int W, cons
  * A caller advances `offset` (< 2^63) by one per step for fresh noise from one seed. */
 int ga_input_erase(const void* x, int x_is_u8, float* out, int B, int CH, int H, int W, const float* mean, const float* std,
                    const int32_t* boxes, int max_count, int mode, uint64_t seed, uint64_t offset, ga_stream_t stream);
+/* timm's collate-time order -- FastCollateMixup on the uint8 batch, PrefetchLoader's normalisation, RandomErasing last on the mixed
+ * image (what every recipe with the prefetcher runs) -- as ONE out-of-place pass over the batch.  The partner of sample b is
+ * B-1-b (B even); every read is of the original x.  mix: DEVICE int32 [B][8], one 32-byte row per sample, drawn by the host
+ * (imagenet_models_amd.FastCollateMixup), so timm's modes 'batch', 'elem' and 'pair' are the same kernel:
+ *   { kind, yl, yh, xl, xh, bits(l), bits(m), 0 }     kind 0 none, 1 mixup, 2 cutmix;  l = fp32 lam, m = its fp32 complement
+ *   (numpy forms m as float32(1.0 - lam) for a scalar lam and as float32(1) - l for a lam vector: an ulp apart, so both travel)
+ *   none:   the sample's own value
+ *   mixup:  u8(rint(fl(fl(a*l) + fl(b*m))))  a = own byte, b = the partner's; three separately rounded fp32 operations (no FMA),
+ *           rint = round half to even (np.rint)
+ *   cutmix: the partner's value inside [yl, yh) x [xl, xh), the own one outside; an empty box is legal.  0 <= yl <= yh <= H and
+ *           0 <= xl <= xh <= W are the host's responsibility: the kernel clamps nothing.
+ * The mixed byte is then normalised with ga_u8_normalize's arithmetic and erased with ga_input_erase's: boxes / max_count / mode /
+ * seed / offset and the Philox counter layout are those of ga_input_erase (the noise index is the flat index of the OUTPUT element);
+ * boxes NULL or max_count 0: no erase.  The result equals ga_input_erase run on the separately mixed uint8 batch, bit for bit.
+ * x_is_u8 == 0: timm's Mixup on an fp32 batch -- the same blend without the rounding to integers, the box copy, no normalisation.
+ * GA_ERR_BAD_ARG: odd B, out == x, H*W % 4 != 0, x not 4 (uint8) / 16-byte aligned, out / mix / boxes not 16-byte aligned, and the
+ * limits of ga_input_erase.
+ *   ga_mixup_target_elem: class indices -> dense [B][NC] for a DEVICE fp32 lam[B]: row b = y1 * lam[b] + y2 * (1 - lam[b]), y2 from
+ *   target[B-1-b]; on / off are formed in double and rounded once; complement, products and sum are separate fp32 roundings. */
+int ga_input_collate(const void* x, int x_is_u8, float* out, int B, int CH, int H, int W, const float* mean, const float* std,
+                     const int32_t* mix, const int32_t* boxes, int max_count, int mode, uint64_t seed, uint64_t offset,
+                     ga_stream_t stream);
+int ga_mixup_target_elem(const int64_t* target, float* out, int B, int NC, const float* lam, double smoothing, ga_stream_t stream);
 /* adaptive gradient clipping (timm adaptive_clip_grad, clip_mode 'agc'): units = int64 {offset, length} pairs into the flat fp32
  * parameter / gradient buffers (a row of a >= 2-d parameter or a whole <= 1-d one); per unit
  * g *= max(|p|, eps) * clip_factor / max(|g|, 1e-6) where |g| exceeds max(|p|, eps) * clip_factor */

@@ -50,7 +50,12 @@ parser.add_argument('--cutmix', type=float, default=1.0, help='cutmix alpha, cut
 parser.add_argument('--cutmix-minmax', type=float, nargs='+', default=None)
 parser.add_argument('--mixup-prob', type=float, default=1.0)
 parser.add_argument('--mixup-switch-prob', type=float, default=0.5)
-parser.add_argument('--mixup-mode', default='batch', help='only "batch" is built')
+parser.add_argument('--mixup-mode', default='batch', help='"batch", "pair" or "elem"; "half" is refused: it halves the batch the '
+                    'engine is planned for')
+parser.add_argument('--collate-mixup', action='store_true', help='the prefetcher order every reference recipe runs: mixup / cutmix on '
+                    'the uint8 batch at collate time (rounded back to uint8), then normalise, then RandomErasing last on the mixed '
+                    'image, as one device pass (timm FastCollateMixup + PrefetchLoader); opt-in, the default order is normalise -> '
+                    'erase -> mixup in fp32')
 parser.add_argument('--mixup-off-epoch', type=int, default=0)
 # RandomErasing on the device (MAP/train.py:214-221; every MAP recipe runs --remode pixel --reprob 0.25)
 parser.add_argument('--reprob', type=float, default=0., metavar='PCT', help='Random erase prob (default: 0.)')
@@ -91,8 +96,8 @@ parser.add_argument('--local_rank', default=0, type=int)
 class SyntheticLoader:
     """fixed-shape random batches generated on the device (seed = args.seed + rank, like timm random_seed)"""
 
-    def __init__(self, batch, steps, num_classes, seed, device, img=224):
-        self.batch, self.steps, self.nc, self.img = batch, steps, num_classes, img
+    def __init__(self, batch, steps, num_classes, seed, device, img=224, uint8=False):
+        self.batch, self.steps, self.nc, self.img, self.uint8 = batch, steps, num_classes, img, uint8
         self.g = torch.Generator(device=device).manual_seed(seed)
         self.device = device
 
@@ -101,7 +106,10 @@ class SyntheticLoader:
 
     def __iter__(self):
         for _ in range(self.steps):
-            x = torch.randn(self.batch, 3, self.img, self.img, device=self.device, generator=self.g)
+            if self.uint8:       # the layout of timm's fast_collate: PrefetchLoader / the collate-time mixup take it from here
+                x = torch.randint(0, 256, (self.batch, 3, self.img, self.img), device=self.device, generator=self.g, dtype=torch.uint8)
+            else:
+                x = torch.randn(self.batch, 3, self.img, self.img, device=self.device, generator=self.g)
             y = torch.randint(0, self.nc, (self.batch,), device=self.device, generator=self.g)
             yield x, y
 
@@ -169,6 +177,11 @@ def main():
                          '(the CPU baseline is the oracle timed by `bench.py`, kind "port")')
     if not args.synthetic:
         raise SystemExit('train.py: only --synthetic data is shipped (no dataset / network in this environment)')
+    if args.mixup_mode == 'half':
+        raise SystemExit("train.py: --mixup-mode half returns half of every batch; the engine is planned for the full batch size, so "
+                         "it is not built ('batch', 'pair' or 'elem')")
+    if args.mixup_mode not in ('batch', 'pair', 'elem'):
+        raise SystemExit(f"train.py: --mixup-mode {args.mixup_mode!r}: 'batch', 'pair' or 'elem'")
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', str(args.local_rank)))
@@ -212,11 +225,20 @@ def main():
     lam = args.dec_lam if args.dec_lam is not None else args.GA_lam
     # mixup / cutmix (GA/train.py:544-557): smoothing then lives in the dense target and the loss is SoftTargetCrossEntropy /
     # BinaryCrossEntropy on it (:616-621)
-    mixup_fn = None
+    # --collate-mixup: the same augmentation in the prefetcher order (FastCollateMixup on the uint8 batch -> normalise -> erase)
+    mixup_fn = collate_mixup = None
     if args.mixup > 0 or args.cutmix > 0. or args.cutmix_minmax is not None:
-        mixup_fn = A.Mixup(mixup_alpha=args.mixup, cutmix_alpha=args.cutmix, cutmix_minmax=args.cutmix_minmax, prob=args.mixup_prob,
-                           switch_prob=args.mixup_switch_prob, mode=args.mixup_mode, label_smoothing=args.smoothing,
-                           num_classes=model.num_classes)
+        mkw = dict(mixup_alpha=args.mixup, cutmix_alpha=args.cutmix, cutmix_minmax=args.cutmix_minmax, prob=args.mixup_prob,
+                   switch_prob=args.mixup_switch_prob, mode=args.mixup_mode, label_smoothing=args.smoothing,
+                   num_classes=model.num_classes)
+        if args.collate_mixup:
+            collate_mixup = A.FastCollateMixup(**mkw)
+        elif args.mixup_mode != 'batch':       # the default order in modes pair / elem: the same pass on the normalised fp32 batch
+            mixup_fn = A.FastCollateMixup(**mkw)
+        else:
+            mixup_fn = A.Mixup(**mkw)
+    elif args.collate_mixup:
+        raise SystemExit('train.py: --collate-mixup needs --mixup > 0, --cutmix > 0 or --cutmix-minmax')
     # RandomErasing as timm's create_loader builds it (re_prob / re_mode / re_count: the MAX count; num_splits 0 without aug-splits)
     random_erasing = None
     if args.reprob > 0.:
@@ -225,17 +247,19 @@ def main():
     step_fn = A.TrainStep(model, opt, args.batch_size, lam=lam, loss='bce' if args.bce_loss else 'ce',
                           smoothing=args.smoothing, grad_accumulation=args.grad_accumulation,
                           clip_grad=args.clip_grad, clip_mode=args.clip_mode, broadcast_buffers=not args.no_ddp_bb,
-                          mixup_fn=mixup_fn, bce_target_thresh=args.bce_target_thresh, comm=comm, random_erasing=random_erasing)
+                          mixup_fn=mixup_fn, bce_target_thresh=args.bce_target_thresh, comm=comm, random_erasing=random_erasing,
+                          collate_mixup=collate_mixup)
     model_ema = A.ModelEma(model, args.model_ema_decay) if args.model_ema else None
     img = getattr(model, 'cfg', {}).get('img_size', 224)
-    loader = SyntheticLoader(args.batch_size, args.steps_per_epoch, model.num_classes, args.seed + rank, 'cuda', img)
+    loader = SyntheticLoader(args.batch_size, args.steps_per_epoch, model.num_classes, args.seed + rank, 'cuda', img,
+                             uint8=collate_mixup is not None)
     eval_loader = SyntheticLoader(args.batch_size, max(1, args.steps_per_epoch // 10), model.num_classes, 7 + rank, 'cuda', img)
     model.train()
     for epoch in range(args.epochs):
         if sched is not None:
             sched.step(epoch)
-        if mixup_fn is not None and args.mixup_off_epoch and epoch >= args.mixup_off_epoch:
-            mixup_fn.mixup_enabled = False      # GA/train.py:705-709
+        if (mixup_fn or collate_mixup) is not None and args.mixup_off_epoch and epoch >= args.mixup_off_epoch:
+            (mixup_fn or collate_mixup).mixup_enabled = False      # GA/train.py:705-709, MAP/train.py:846-850
         train_metrics = train_one_epoch(epoch, step_fn, loader, args, world, rank, model_ema)
         if world > 1 and args.dist_bn in ('broadcast', 'reduce'):
             A.distribute_bn(model, world, args.dist_bn == 'reduce')
