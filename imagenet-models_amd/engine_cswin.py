@@ -1,6 +1,6 @@
 """CSWinEngine: the static launch plans (weight prep / forward / backward) of one GA_CSWinTransformer for a fixed
-(batch, train|eval, math mode).  Shares buffers, BatchNorm / GroupConvMlp helpers and the whole GA head with
-engine.GAEngine; the trunk is restated here from /root/reference/GA/ga_cswin.py:
+(batch, train|eval, math mode): engine_base.EngineBase (buffers, plans, BatchNorm helpers) + engine.GAHeads (aggregation,
+SE-Bottleneck, GroupConvMlp, the whole GA head); the trunk is restated here from /root/reference/GA/ga_cswin.py:
 
   deep stem :463-477 ........ NCHW fp32 -> NHWC8 pack, three 3x3 convs as gather GEMMs (s2, s1, s2), LayerNorm+GELU fused
   CSWinBlock :191-212 ....... LN1 (affine folded into qkv) -> qkv GEMM -> stripe attention + LePE (one kernel for both
@@ -20,7 +20,8 @@ import os
 import torch
 
 from . import ops
-from .engine import GAEngine, pad8
+from .engine import GAHeads
+from .engine_base import EngineBase, pad8
 from .ops import A_CONV3, A_CONV3S2, A_NEIGH2, ACT_GELU, C_UNPATCH2
 
 
@@ -34,7 +35,7 @@ def tap_after(nblocks, naggre):
     return taps
 
 
-class CSWinEngine(GAEngine):
+class CSWinEngine(GAHeads, EngineBase):
     # ------------------------------------------------------------------------------------------
     def _drop_path_rates(self):
         """ga_cswin.py:486 (linspace over the 4 trunk stages), :538,571 (stage5 and gram layers: dpr[-1]), :541 (Bottleneck:
@@ -61,7 +62,7 @@ class CSWinEngine(GAEngine):
     # ------------------------------------------------------------------------------------------
     def _cs_block_fwd(self, pre, x, mod):
         """x [B*reso*reso, C] -> block output (same shape); mod = the block's parameter holder (geometry).  Inside a forward chain
-        (GAEngine._chains: the trunk recorded once per batch part, each part on its own lane) the launches cover the chain's rows of
+        (EngineBase._chains: the trunk recorded once per batch part, each part on its own lane) the launches cover the chain's rows of
         the same full-batch buffers; weight preparation and the saved state are recorded by the first pass only"""
         F, dt, B, P, T = self.fwd, self.dt, self.B, self.P, self.training
         C, reso, heads, mg = mod.dim, mod.reso, mod.num_heads, mod.mlp_groups
@@ -71,7 +72,7 @@ class CSWinEngine(GAEngine):
         (lane, r0, r1, b0, b1), = self._fsplits(HW)
         first = pre not in self.blocks
         assert mg == 1 or (r0 == 0 and r1 == M), 'grouped-MLP blocks are recorded for the whole batch'
-        if getattr(self, '_chain', None) is not None:      # (outside a chain the caller's lane stands: the heads' gram_layer blocks)
+        if self._chain is not None:      # (outside a chain the caller's lane stands: the heads' gram_layer blocks)
             F.lane = lane
         dp1, dp2 = self.dp_scale.get(pre + '#1'), self.dp_scale.get(pre + '#2')
         dp1c = dp1[b0:b1] if dp1 is not None else None
@@ -91,7 +92,7 @@ class CSWinEngine(GAEngine):
         lepe = [(P[pre + f'attns.{i}.get_v.weight'], P[pre + f'attns.{i}.get_v.bias']) for i in range(mod.branch_num)]
         if first:      # the backward's descriptor: the whole batch
             st['desc'] = F.cswin_desc(st['qkv'], st['att'], B, reso, C, heads, mod.stripes(), lepe, (C // heads) ** -0.5, dt)
-            self._lepe_ws_elems = max(getattr(self, '_lepe_ws_elems', 0), ops.cswin_attn_bwd_workspace(st['desc']) // 4)
+            self._lepe_ws_elems = max(self._lepe_ws_elems, ops.cswin_attn_bwd_workspace(st['desc']) // 4)
         dfw = st['desc'] if (r0 == 0 and r1 == M) else F.cswin_desc(st['qkv'][r0:r1], st['att'][r0:r1], b1 - b0, reso, C, heads,
                                                                        mod.stripes(), lepe, (C // heads) ** -0.5, dt)
         F.cswin_attn_fwd(dfw, label=pre + 'attn')
@@ -136,7 +137,7 @@ class CSWinEngine(GAEngine):
         dp1, dp2 = self.dp_scale.get(pre + '#1'), self.dp_scale.get(pre + '#2')
         # trunk blocks: the weight-gradient launches go to the plan's asynchronous lane (nothing on the dgrad chain reads their
         # results); two sets of the transients they read + three rotating dx buffers (caller), so this block only waits for the
-        # asynchronous launches of the block before the previous one (same scheme as GAEngine._block_bwd)
+        # asynchronous launches of the block before the previous one (same scheme as ConvNeXtTrunk._block_bwd)
         side = self.async_wgrad and Bk.lane == 0
         par = ''
         if side:
@@ -235,7 +236,7 @@ class CSWinEngine(GAEngine):
         Mo = B * Ho * Ho
         (lane, r0, r1, b0, b1), = self._fsplits(Ho * Ho)           # output rows of this forward chain (whole images)
         i0, i1 = b0 * Hin * Hin, b1 * Hin * Hin
-        if getattr(self, '_chain', None) is not None:
+        if self._chain is not None:
             F.lane = lane
         Wf = self._w_plain(cname + 'weight', Cout, Cin, 3, 3, need_T=False)
         st = dict(x=x, Hin=Hin, Cin=Cin, Cout=Cout, cname=cname, nname=nname, bias=bias)
@@ -282,18 +283,15 @@ class CSWinEngine(GAEngine):
         B, T, F, dt, P = self.B, self.training, self.fwd, self.dt, self.P
         e, d, dep = cfg['embed_dim'], cfg['dims'], cfg['depth']
         img = self.img
+        self._init_group_mlp()
+        self._lepe_ws_elems = 0      # floats of the largest LePE weight-gradient partial buffer a block's backward asks for
         if T:
             F.zero(self.bn_pool, label='zero.bn_sums')
         # ---------------- deep stem (ga_cswin.py:463-477) ----------------
         sp = 'stage1_conv_embed.'
         H1 = img // 2
         M1 = B * H1 * H1
-        self.x8 = self.buf('stem.x8', (B * img * img, 8))
-        self.x_placeholder = torch.zeros(8, device=self.dev)
-        F.nchw3_to_nhwc8(self.x_placeholder, self.x8, B, img, img, dt, label='stem.pack')
-        self.pack_call = len(F.calls) - 1
-        W0 = self.buf('w.' + sp + '0', (e, 72))
-        self.prep.convw_pack(P[sp + '0.weight'], W0, e, 3, 9, 8, 72, dt, label='prep.' + sp + '0')
+        W0 = self._image_pack8_stem(sp + '0', e)
         W1 = self._w_plain(sp + '5.weight', e, e, 3, 3, flip=True)
         S = self.stem = {}
         S['c0'] = self.act(sp + 'c0', (M1, e))
@@ -304,7 +302,7 @@ class CSWinEngine(GAEngine):
         S['m1'], S['r1'] = self.act(sp + 'm1', (M1,), torch.float32), self.act(sp + 'r1', (M1,), torch.float32)
         stages = [m.stage1, m.stage2, m.stage3, m.stage4]
         taps_at = tap_after(dep[2], cfg['naggre'])
-        # one pass per forward chain (batch part, GAEngine._chains): with GAEXT_FWD_SPLIT > 1 the deep stem and the four stages run as
+        # one pass per forward chain (batch part, EngineBase._chains): with GAEXT_FWD_SPLIT > 1 the deep stem and the four stages run as
         # independent chains on side streams -- every op of the trunk is per image, and its launches are too small to fill the chip
         # alone (the step timeline had one kernel running for 23 of 39 ms); every pass names the same full-batch buffers
         chains = self._chains()
@@ -339,19 +337,9 @@ class CSWinEngine(GAEngine):
         # ---------------- aggregate (ga_cswin.py:666-669) ----------------
         Hc = img // 16
         M4 = B * Hc * Hc
-        ctot = sum(d) + d[2] * cfg['naggre']
         assert len(taps) == cfg['naggre'], (len(taps), cfg['naggre'])
-        cat = self.act('agg.cat', (M4, ctot))
-        segs = [(feats[0][0], feats[0][1], d[0], 0), (feats[1][0], feats[1][1], d[1], 0)]
-        segs += [(t, feats[2][1], d[2], 0) for t, _ in taps]
-        segs += [(feats[2][0], feats[2][1], d[2], 0), (feats[3][0], feats[3][1], d[3], 1)]
-        off = 0
-        self.agg_segs = []
-        for src, hw, c, mode in segs:
-            F.pool_concat_fwd(src, cat, B, hw, hw, c, Hc, Hc, ctot, off, mode, dt, label=f'agg.{off}')
-            self.agg_segs.append((src, hw, c, mode, off))
-            off += c
-        assert off == ctot
+        cat, ctot = self._aggregate_fwd(feats, [t for t, _ in taps], d, Hc)
+        assert ctot == sum(d) + d[2] * cfg['naggre']
         # ---------------- stage5 ----------------
         cur = d[3]
         self.cout = cur
@@ -367,17 +355,12 @@ class CSWinEngine(GAEngine):
             L['t5'] = t5
             x4 = self._cs_block_fwd('stage5.2.', t5, m.stage5[2])
         else:
-            self.bott_prefix = 'stage5.'
-            x4 = self._bottleneck_fwd(cat, M4, ctot, cur)
+            x4 = self._bottleneck_fwd(cat, M4, ctot, cur, pre='stage5.')
         # ---------------- heads ----------------
         self._build_heads(x4, M4, Hc)
         # ---------------- backward ----------------
         if T:
             self._build_backward(feats, taps, x4, M4, ctot, cat)
-            if self.async_wgrad:
-                self.bwd.join_async()
-            self.bwd.flush('end.')
-        self.prep.flush('prep.')
 
     # ------------------------------------------------------------------------------------------
     # grouped gram_contraction of all heads (ga_cswin.py:559-561): ONE batched GEMM, batch = heads x 8 groups
@@ -491,11 +474,7 @@ class CSWinEngine(GAEngine):
         self._unpad_all()
         Bk.mark('heads')      # every gradient of stage5 / gram_* / ga / fc is final here
         # aggregate backward -> gradient seeds of the stage outputs / taps
-        seeds = []
-        for src, hw, c, mode, off in self.agg_segs:
-            ds = self.buf(f'agg.d{off}', (B * hw * hw, c))
-            Bk.pool_concat_bwd(dcat, None, ds, B, hw, hw, c, 14, 14, ctot, off, mode, dt, label=f'agg.b{off}')
-            seeds.append(ds)
+        seeds = self._aggregate_bwd(dcat, ctot, 14)
         ntap = len(taps)
         d_taps = {j: seeds[2 + i] for i, (_, j) in enumerate(taps)}
         seed = {0: seeds[0], 1: seeds[1], 2: seeds[2 + ntap], 3: seeds[3 + ntap]}
@@ -548,14 +527,3 @@ class CSWinEngine(GAEngine):
         with self._wlane():
             Bk.wgrad(dc0, self.x8, G0, M1, e, 72, dt, x_kind=A_CONV3S2, x_dims=(self.img, self.img, 8), label=sp + 'conv0.wg')
             Bk.convw_unpack_grad(G0, self.grad(sp + '0.weight'), e, 3, 9, 8, 72, label=sp + 'conv0.unf')   # same lane: after the wgrad
-
-    # ------------------------------------------------------------------------------------------
-    def set_input(self, x):
-        x = self._normalize_u8(x)
-        assert x.is_cuda and x.dtype == torch.float32 and tuple(x.shape) == (self.B, 3, self.img, self.img), \
-            f'input must be a float32 CUDA tensor of shape {(self.B, 3, self.img, self.img)}, got {tuple(x.shape)} {x.dtype}'
-        if not x.is_contiguous():
-            x = x.contiguous()
-        self.x_ref = x
-        fn, args, label = self.fwd.calls[self.pack_call]
-        self.fwd.calls[self.pack_call] = (fn, (x.data_ptr(),) + tuple(args[1:]), label)

@@ -1,6 +1,6 @@
-"""MAPEngine: the static launch plans (weight prep / forward / backward) of one MAP_ConvNeXt for a fixed
-(batch, train|eval, math mode).  The ConvNeXt trunk is engine.GAEngine's (same kernels, the FB parameter names of
-/root/reference/MAP/models/map_convnext.py:16-83); the head is restated here from /root/reference/MAP/models/map.py:
+"""MAPHead: the builder of the MAP head, composed with EngineBase and a trunk into MAPEngine (here), MAPViTEngine, MAPPiTEngine,
+ResNetEngine and MobileNetEngine.  MAPEngine: the launch plans of one MAP_ConvNeXt -- engine.ConvNeXtTrunk under the FB parameter
+names of /root/reference/MAP/models/map_convnext.py:16-83 and this head, restated from /root/reference/MAP/models/map.py:
 
   MultiScale :322-333 ....... five maps resized to 14 x 14 (bilinear REDUCTION of the larger ones, adaptive-avg-pool
                               ENLARGEMENT of the 7 x 7 one) into one concat buffer -> conv1x1 -> BN -> GELU
@@ -20,12 +20,13 @@ import os
 import torch
 
 from . import ops  # noqa: F401
-from .engine import GAEngine, pad8
+from .engine import ConvNeXtTrunk, GroupMlp
+from .engine_base import EngineBase, pad8
 from .ops import Plan
 
 
-class MAPEngine(GAEngine):
-    HP = 'head.'        # parameter-name prefix of the MAPHead (MobileNetV1 holds it as `fc.`)
+class FBConvNeXtTrunk(ConvNeXtTrunk):
+    """the ConvNeXt trunk under the FB module names and DropPath schedule of map_convnext.py (MAP-ConvNeXt, plain ConvNeXt)"""
     NAMES = dict(stem_conv='downsample_layers.0.0.', stem_ln='downsample_layers.0.1.', ds_ln='downsample_layers.{i}.0.',
                  ds_conv='downsample_layers.{i}.1.', block='stages.{i}.{j}.', dw='dwconv.', fc1='pwconv1.', fc2='pwconv2.')
 
@@ -35,34 +36,50 @@ class MAPEngine(GAEngine):
         pts = torch.linspace(0, rate, sum(dep)).split(list(dep))
         return {f'stages.{i}.{j}.': float(pts[i][j]) for i in range(4) for j in range(dep[i])}
 
-    # ------------------------------------------------------------------------------------------
-    def _build(self):
-        cfg = self.cfg
-        d = cfg['dims']
-        B, T, F, dt, P = self.B, self.training, self.fwd, self.dt, self.P
-        feats, taps, stage_in, x_stem = self._build_trunk()
-        # ---------------- MultiScale (map.py:322-333) ----------------
-        Hc = 14
-        M4 = B * Hc * Hc
-        L = cfg['last_dim']
-        srcs = [(x_stem, self.img // 4, d[0])] + [(x, res, d[i]) for i, (x, res) in enumerate(feats)]
+
+class MAPHead(GroupMlp):
+    """builder: MultiScale, the CAP groups and the NormHeads on a trunk's feature maps; with dropout in the head, its own mask
+    sampling in front of the forward and the (org, avg) form of the fused loss"""
+    HP = 'head.'        # parameter-name prefix of the MAPHead (MobileNetV1 holds it as `fc.`)
+
+    def _ms_concat_fwd(self, srcs, Hc, labels=None):
+        """MultiScale (map.py:322-333): the maps srcs = [(x, side, channels)] resized to Hc x Hc into the columns of one concat
+        buffer -- copied, reduced (bilinear: ga_pool_concat for an integer factor, else the general ga_resize_concat) or enlarged
+        (adaptive average pool); labels: the launches' labels where they are not 'agg.<column offset>'.  Returns (cat, ctot)."""
+        B, F, dt = self.B, self.fwd, self.dt
+        self.Hc = Hc
         ctot = sum(c for _, _, c in srcs)
-        cat = self.act('ms.cat', (M4, ctot))
-        off = 0
-        self.agg_segs = []
-        for src, hw, c in srcs:
-            mode = 0 if hw == Hc else (2 if hw > Hc else 3)
-            F.pool_concat_fwd(src, cat, B, hw, hw, c, Hc, Hc, ctot, off, mode, dt, label=f'agg.{off}')
+        cat = self.act('ms.cat', (B * Hc * Hc, ctot))
+        self.agg_segs, off = [], 0
+        for j, (src, hw, c) in enumerate(srcs):
+            if hw == Hc:
+                mode = 0
+            elif hw < Hc:
+                assert Hc % hw == 0, 'adaptive_avg_pool2d enlargement by a non-integer factor is not on the registered path'
+                mode = 3
+            else:
+                mode = 2 if hw % Hc == 0 else 'resize'
+            label = labels[j] if labels else f'agg.{off}'
+            if mode == 'resize':
+                F.resize_concat_fwd(src, cat, B, hw, hw, c, Hc, Hc, ctot, off, dt, label=label)
+            else:
+                F.pool_concat_fwd(src, cat, B, hw, hw, c, Hc, Hc, ctot, off, mode, dt, label=label)
             self.agg_segs.append((src, hw, c, mode, off))
             off += c
-        x = self._multi_scale_conv_fwd(cat, M4, ctot)
-        self._build_map_head(x, M4, Hc)
-        if T:
-            self._build_backward(feats, stage_in, x, M4)
-            if self.async_wgrad:
-                self.bwd.join_async()
-            self.bwd.flush('end.')
-        self.prep.flush('prep.')
+        return cat, ctot
+
+    def _ms_concat_bwd(self, dcat):
+        """gradient of every map of _ms_concat_fwd, in its order"""
+        Bk, B, dt, Hc, ctot = self.bwd, self.B, self.dt, self.Hc, self.ms['ctot']
+        seeds = []
+        for src, hw, c, mode, off in self.agg_segs:
+            ds = self.buf(f'agg.d{off}', (B * hw * hw, c))
+            if mode == 'resize':
+                Bk.resize_concat_bwd(dcat, ds, B, hw, hw, c, Hc, Hc, ctot, off, dt, label=f'agg.b{off}')
+            else:
+                Bk.pool_concat_bwd(dcat, None, ds, B, hw, hw, c, Hc, Hc, ctot, off, mode, dt, label=f'agg.b{off}')
+            seeds.append(ds)
+        return seeds
 
     def _multi_scale_conv_fwd(self, cat, M4, ctot):
         """MultiScale.concat_conv (map.py:322-333): conv1x1 -> BN -> GELU on the concat of the resized maps"""
@@ -90,6 +107,7 @@ class MAPEngine(GAEngine):
     # ------------------------------------------------------------------------------------------
     def _build_map_head(self, x, M4, Hc):
         cfg, B, T, F, dt, P = self.cfg, self.B, self.training, self.fwd, self.dt, self.P
+        self._init_group_mlp()
         L, G, Tn, E, nh = cfg['last_dim'], cfg['n_groups'], cfg['n_tokens'], cfg['ca_dim'], cfg['num_heads']
         bp, NC = cfg['bp_dim'], cfg['num_classes']
         sdt = self.sdt = bool(cfg.get('self_distill_token', True))     # CAP's extra mean token + MAPHead.self_dt_heads (map.py:273-275,490-491)
@@ -442,19 +460,6 @@ class MAPEngine(GAEngine):
         self._bn_bwd(gp + 'ch_reduction.1.', h['bn_gc'], dg0, None, h['gc'], gcn['dout'][:, k * bp:], M4, bp, ldx=gcn['ld'],
                      lddx=gcn['ld'])
 
-    # ------------------------------------------------------------------------------------------
-    def _build_backward(self, feats, stage_in, x, M4):
-        """head backward, then the ConvNeXt trunk's"""
-        Bk, dt, B = self.bwd, self.dt, self.B
-        dcat = self._build_head_backward(x, M4)
-        ctot = self.ms['ctot']
-        seeds = []
-        for src, hw, c, mode, off in self.agg_segs:
-            ds = self.buf(f'agg.d{off}', (B * hw * hw, c))
-            Bk.pool_concat_bwd(dcat, None, ds, B, hw, hw, c, 14, 14, ctot, off, mode, dt, label=f'agg.b{off}')
-            seeds.append(ds)
-        self._build_trunk_backward({i: seeds[1 + i] for i in range(4)}, [], [], feats, stage_in, stem_seed=seeds[0])
-
     def _build_head_backward(self, x, M4):
         """classifiers, the groups, ch_reduction / k|v stacks, MultiScale conv: everything of head.* ; returns dcat [M4, ctot], the
         gradient of the multi-scale concat (the trunk-specific part takes it from there)"""
@@ -534,12 +539,13 @@ class MAPEngine(GAEngine):
         if self.async_wgrad:
             Bk.join_async()
         Bk.flush('heads.')
+        assert not self.pgrad, 'padded parameter gradients are not copied back on this path'
         Bk.mark('heads')      # every gradient of head.* is final here
         return dcat
 
     # ------------------------------------------------------------------------------------------
     def forward(self, x):
-        if self.training and self.drop and not getattr(self, 'fixed_masks', False):
+        if self.training and self.drop and not self.fixed_masks:
             self.drop['plan'].run()
         return super().forward(x)
 
@@ -559,3 +565,17 @@ class MAPEngine(GAEngine):
         if not self.sdt:         # plain list of group logits: multi_group_loss reduces to the GA form (MAP/train.py:818-820,824-837)
             return self.logits[:G], None, self.dlogits[:G], None, G
         return self.logits[:G], self.logits[G:], self.dlogits[:G], self.dlogits[G:], G
+
+
+class MAPEngine(FBConvNeXtTrunk, MAPHead, EngineBase):
+    def _build(self):
+        d = self.cfg['dims']
+        feats, taps, stage_in, x_stem = self._build_trunk()
+        Hc = 14
+        M4 = self.B * Hc * Hc
+        cat, ctot = self._ms_concat_fwd([(x_stem, self.img // 4, d[0])] + [(x, res, d[i]) for i, (x, res) in enumerate(feats)], Hc)
+        x = self._multi_scale_conv_fwd(cat, M4, ctot)
+        self._build_map_head(x, M4, Hc)
+        if self.training:      # head backward, then the ConvNeXt trunk's
+            seeds = self._ms_concat_bwd(self._build_head_backward(x, M4))
+            self._build_trunk_backward({i: seeds[1 + i] for i in range(4)}, [], [], feats, stage_in, stem_seed=seeds[0])

@@ -6,7 +6,7 @@
                                        ga_gemm (+ sums) -> finalize -> affine + ReLU
   plain head (:89-93) ................ ga_spatial_sum (global average pool) -> Linear (ga_gemm, fp32 logits); backward ga_rows_bcast
   MAP head (:67-83) .................. channel_convertor (1 x 1 conv -> BN -> ReLU, map.py:356-364) on the 7 x 7 map, then
-                                       MAPEngine._build_map_head (one group, four tokens, interactive attention, mlp_ratio 1)
+                                       MAPHead._build_map_head (one group, four tokens, interactive attention, mlp_ratio 1)
 
 Backward mirrors it: ga_bn_bwd_reduce / _apply with the stored ReLU output as the mask, the pointwise data gradient through the
 transposed weight copy of ga_weight_prep, ga_wgrad for the pointwise and stem weights and ga_dwconv3_bwd_data / _bwd_weight for the
@@ -16,12 +16,12 @@ statistics and updates the running ones (momentum 0.1, eps 1e-5); eval-mode Batc
 import torch
 
 from . import ops  # noqa: F401
-from .engine import GAEngine, pad8
-from .engine_map import MAPEngine
+from .engine_base import EngineBase, pad8
+from .engine_map import MAPHead
 from .ops import A_CONV3S2
 
 
-class MobileNetEngine(MAPEngine):
+class MobileNetEngine(MAPHead, EngineBase):
     HP = 'fc.'
 
     def _drop_path_rates(self):
@@ -31,8 +31,6 @@ class MobileNetEngine(MAPEngine):
         cfg = self.cfg
         B, T, F, dt, P = self.B, self.training, self.fwd, self.dt, self.P
         img = self.img
-        NC = cfg['num_classes']
-        assert NC % 8 == 0, 'num_classes must be a multiple of 8 (pad the classifier)'
         assert self.sync_bn is None, 'SyncBatchNorm is not on the MobileNetV1 path'
         if T:
             F.zero(self.bn_pool, label='zero.bn_sums')
@@ -40,12 +38,7 @@ class MobileNetEngine(MAPEngine):
         sp, C0 = 'layers.0.0.', cfg['stem_ch']
         H = (img - 1) // 2 + 1
         M = B * H * H
-        self.x8 = self.buf('stem.x8', (B * img * img, 8))
-        self.x_placeholder = torch.zeros(8, device=self.dev)
-        F.nchw3_to_nhwc8(self.x_placeholder, self.x8, B, img, img, dt, label='stem.pack')
-        self.pack_call = len(F.calls) - 1
-        W0 = self.buf('w.' + sp + '0', (C0, 72))
-        self.prep.convw_pack(P[sp + '0.weight'], W0, C0, 3, 9, 8, 72, dt, label='prep.' + sp + '0')
+        W0 = self._image_pack8_stem(sp + '0', C0)
         st = self.stem = dict(c=self.act(sp + 'c', (M, C0)), bn=self._bn_bufs(sp + '1.', C0), a=self.act(sp + 'a', (M, C0)), M=M, C=C0)
         F.gemm(self.x8, W0, st['c'], M, C0, 72, dt, a_kind=A_CONV3S2, a_dims=(img, img, 8), colsum=st['bn']['s'] if T else None,
                colsumsq=st['bn']['q'] if T else None, label=sp + 'conv')
@@ -71,20 +64,14 @@ class MobileNetEngine(MAPEngine):
             self.xh = self._conv1x1_bn_act_fwd(x4, M4, C4, self.HP + 'mmcap.channel_convertor.', 'relu')
             self._build_map_head(self.xh, M4, H4)
         else:
-            self.drop, self.G = None, 1
+            self.drop, self.G, self.sdt = None, 1, False         # the plain Linear: one group of logits, no dropout, no mean token
             pool32 = self.tmp('head.pool32', (B, C4), torch.float32)         # ga_spatial_sum reduces into fp32
             self.pool = self.act('head.pool', (B, C4))
             F.spatial_sum(x4, None, pool32, B, H4 * H4, C4, 1.0 / (H4 * H4), dt, label='fc.pool')
             F.cast_from_f32(pool32, self.pool, B * C4, dt, label='fc.pool.cast')
-            Wh = self._w_plain('fc.2.weight', NC, C4, 1, 1)
-            self.logits = self.buf('logits', (1, B, NC), torch.float32)
-            F.gemm(self.pool, Wh, self.logits[0], B, NC, C4, dt, bias=P['fc.2.bias'], c_f32=True, label='fc.2')
+            self._linear_head_fwd(self.pool, 'fc.2.', C4, 'fc.2')
         if T:
             self._build_mobilenet_backward(x4, M4, H4, C4)
-            if self.async_wgrad:
-                self.bwd.join_async()
-            self.bwd.flush('end.')
-        self.prep.flush('prep.')
 
     def _conv_dw_fwd(self, pre, x, H, cin, cout, s):
         """conv_dw (map_mobilenet.py:25-37): depthwise 3 x 3 / s -> BN -> ReLU -> 1 x 1 -> BN -> ReLU"""
@@ -113,14 +100,8 @@ class MobileNetEngine(MAPEngine):
         if cfg['use_map']:
             dy = self._build_head_backward(self.xh, M4)      # zeroes the arena, marks 'heads'; the gradient wrt the last map
         else:
-            NC = cfg['num_classes']
             Bk.zero(self.arena, label='zero.arena')
-            self.dlogits = self.buf('dlogits', (1, B, NC))
-            dl = self.dlogits[0]
-            with self._wlane():
-                Bk.wgrad(dl, self.pool, self.grad('fc.2.weight'), B, NC, C4, dt, dbias=self.grad('fc.2.bias'), label='fc.2.wg')
-            dpool = self.tmp('head.dpool', (B, C4))
-            Bk.gemm(dl, self.W['fc.2.weight.T'], dpool, B, C4, NC, dt, ldb=pad8(NC), label='fc.2.dg')
+            dpool = self._linear_head_bwd(self.pool, 'fc.2.', C4, 'head.dpool')
             dy = self.buf('head.seed', (M4, C4))
             Bk.rows_bcast(dpool, dy, B, H4 * H4, C4, 1.0 / (H4 * H4), dt, label='fc.poolb')
             if self.async_wgrad:
@@ -163,17 +144,3 @@ class MobileNetEngine(MAPEngine):
             Bk.dwconv3_bwd_weight(dd, u['x'], self.grad(pre + '0.weight'), B, H, H, cin, s, dt, label=pre + 'dw.wg')
         Bk.dwconv3_bwd_data(dd, P[pre + '0.weight'], dx, B, H, H, cin, s, dt, label=pre + 'dw.dg')
         return dx
-
-    # ------------------------------------------------------------------------------------------
-    def set_input(self, x):
-        x = self._normalize_u8(x)
-        assert x.is_cuda and x.dtype == torch.float32 and tuple(x.shape) == (self.B, 3, self.img, self.img), \
-            f'input must be a float32 CUDA tensor of shape {(self.B, 3, self.img, self.img)}, got {tuple(x.shape)} {x.dtype}'
-        if not x.is_contiguous():
-            x = x.contiguous()
-        self.x_ref = x
-        fn, args, label = self.fwd.calls[self.pack_call]
-        self.fwd.calls[self.pack_call] = (fn, (x.data_ptr(),) + tuple(args[1:]), label)
-
-    def _loss_operands(self):
-        return MAPEngine._loss_operands(self) if self.cfg['use_map'] else GAEngine._loss_operands(self)

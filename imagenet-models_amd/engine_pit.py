@@ -1,5 +1,5 @@
-"""MAPPiTEngine: launch plans of the pooling transformer of /root/reference/MAP/models/map_pit.py (PoolingTransformer with
-pool_type='map', :84-201) feeding the MAP head (engine_map.MAPEngine).
+"""PiTTrunk: the builder of the pooling transformer of /root/reference/MAP/models/map_pit.py (PoolingTransformer, :84-201).
+MAPPiTEngine: that trunk feeding the MAP head (pool_type='map'; engine_map.MAPHead).
 
   conv_embedding (:71-81, 16 x 16 / stride 8, overlapping) ... ga_patchify_strided + ga_gemm (bias in the epilogue)
   + pos_embed (:190-191, an NCHW parameter) ..................... transposed once per step to [HW][C]; ga_pos_add_fwd / _bwd
@@ -17,11 +17,14 @@ Linear (ga_gemm, fp32 logits); backward: classifier weight gradient / dgrad, ga_
 import torch
 
 from . import ops  # noqa: F401
-from .engine import GAEngine, pad8
-from .engine_vit import MAPViTEngine
+from .engine_base import EngineBase
+from .engine_map import MAPHead
+from .engine_vit import ViTBlocks
 
 
-class MAPPiTEngine(MAPViTEngine):
+class PiTTrunk(ViTBlocks):
+    """builder: conv_embedding + pos_embed and the three transformer stages with their pooling convolutions, forward and backward"""
+
     def _drop_path_rates(self):
         """map_pit.py:116-118: drop_path_rate * i / total_block; timm's Block applies it to both residual branches"""
         cfg = self.cfg
@@ -37,7 +40,7 @@ class MAPPiTEngine(MAPViTEngine):
         returns the feature list [(map, side, channels)] = [embedding, stage 0, stage 1, stage 2] and the patch row length"""
         cfg = self.cfg
         B, T, F, dt, P = self.B, self.training, self.fwd, self.dt, self.P
-        self.img = img = self._img
+        img = self.img
         dims, depth, heads, ps, stride, w0 = cfg['dims'], cfg['depth'], cfg['heads'], cfg['patch_size'], cfg['stride'], cfg['width']
         K0 = 3 * ps * ps
         C0, Mp0 = dims[0], B * w0 * w0
@@ -46,14 +49,14 @@ class MAPPiTEngine(MAPViTEngine):
         # ---------------- conv_embedding + pos_embed ----------------
         self.x_placeholder = torch.zeros(B, 3, img, img, device=self.dev)
         patches = self.patches = self.act('patch.cols', (Mp0, K0))
+        self.input_call = len(F.calls)
         F.patchify_strided(self.x_placeholder, patches, ps, stride, dt, label='patch.pack')
-        self.pack_call = len(F.calls) - 1
         Wpe = self._w_plain('patch_embed.conv.weight', C0, K0, 1, 1, need_T=False)
         tok = self.tmp('patch.tok', (Mp0, C0))
         posT = self.buf('w.posT', (w0 * w0, C0), torch.float32)
         self.prep.transpose_f32(P['pos_embed'], posT, C0, w0 * w0)
         x0 = self.buf('embed.x0', (Mp0, C0))
-        # ---------------- embedding + stages: one pass per forward chain (batch part on its own lane, GAEngine._chains) ----------------
+        # ---------------- embedding + stages: one pass per forward chain (batch part on its own lane, EngineBase._chains) ----------------
         chains = self._chains()
         for chain in chains:
             self._chain = chain if len(chains) > 1 else None
@@ -82,53 +85,6 @@ class MAPPiTEngine(MAPViTEngine):
         self._chain = None
         F.lane = 0
         return feats, K0
-
-    def _build(self):
-        cfg = self.cfg
-        B, T, F, dt = self.B, self.training, self.fwd, self.dt
-        feats, K0 = self._build_pit_trunk()
-        # ---------------- MultiScale at the size of feature `multi_scale_level` (map.py:322-333) ----------------
-        Hc = self.Hc = feats[cfg['multi_scale_level']][1]
-        M4 = B * Hc * Hc
-        ctot = sum(c for _, _, c in feats)
-        cat = self.act('ms.cat', (M4, ctot))
-        self.agg_segs, off = [], 0
-        for fm, fhw, c in feats:
-            if fhw == Hc:
-                mode = 0
-            elif fhw < Hc:
-                assert Hc % fhw == 0, 'adaptive_avg_pool2d enlargement by a non-integer factor is not on the registered path'
-                mode = 3
-            else:
-                mode = 2 if fhw % Hc == 0 else 'resize'
-            if mode == 'resize':
-                F.resize_concat_fwd(fm, cat, B, fhw, fhw, c, Hc, Hc, ctot, off, dt, label=f'agg.{off}')
-            else:
-                F.pool_concat_fwd(fm, cat, B, fhw, fhw, c, Hc, Hc, ctot, off, mode, dt, label=f'agg.{off}')
-            self.agg_segs.append((fm, fhw, c, mode, off))
-            off += c
-        xh = self._multi_scale_conv_fwd(cat, M4, ctot)
-        self._build_map_head(xh, M4, Hc)
-        if T:
-            self._build_pit_backward(xh, M4, K0)
-            if self.async_wgrad:
-                self.bwd.join_async()
-            self.bwd.flush('end.')
-        self.prep.flush('prep.')
-
-    def _build_pit_backward(self, xh, M4, K0):
-        Bk, dt, B = self.bwd, self.dt, self.B
-        dcat = self._build_head_backward(xh, M4)
-        ctot = self.ms['ctot']
-        seeds = []
-        for fm, fhw, c, mode, off in self.agg_segs:
-            ds = self.buf(f'agg.d{off}', (B * fhw * fhw, c))
-            if mode == 'resize':
-                Bk.resize_concat_bwd(dcat, ds, B, fhw, fhw, c, self.Hc, self.Hc, ctot, off, dt, label=f'agg.b{off}')
-            else:
-                Bk.pool_concat_bwd(dcat, None, ds, B, fhw, fhw, c, self.Hc, self.Hc, ctot, off, mode, dt, label=f'agg.b{off}')
-            seeds.append(ds)
-        self._build_pit_trunk_backward(seeds, K0)
 
     def _build_pit_trunk_backward(self, seeds, K0):
         """seeds[i]: gradient wrt feature i of _build_pit_trunk's list (None: the head does not read that feature); seeds[3], the
@@ -180,30 +136,32 @@ class MAPPiTEngine(MAPViTEngine):
                      dbias=self.grad('patch_embed.conv.bias'), label='patch.wg')
 
 
-class PiTEngine(MAPPiTEngine):
+class MAPPiTEngine(PiTTrunk, MAPHead, EngineBase):
     def _build(self):
-        cfg = self.cfg
-        B, T, F, dt, P = self.B, self.training, self.fwd, self.dt, self.P
-        NC = cfg['num_classes']
-        assert NC % 8 == 0, 'num_classes must be a multiple of 8 (pad the classifier)'
-        self.drop = None
-        self.G = 1
+        B = self.B
+        feats, K0 = self._build_pit_trunk()
+        # ---------------- MultiScale at the size of feature `multi_scale_level` (map.py:322-333) ----------------
+        Hc = feats[self.cfg['multi_scale_level']][1]
+        M4 = B * Hc * Hc
+        cat, ctot = self._ms_concat_fwd(feats, Hc)
+        xh = self._multi_scale_conv_fwd(cat, M4, ctot)
+        self._build_map_head(xh, M4, Hc)
+        if self.training:
+            self._build_pit_trunk_backward(self._ms_concat_bwd(self._build_head_backward(xh, M4)), K0)
+
+
+class PiTEngine(PiTTrunk, EngineBase):
+    def _build(self):
+        B, F, dt = self.B, self.fwd, self.dt
         feats, K0 = self._build_pit_trunk()
         x3, hw, C = feats[-1]                                 # forward_head reads the last feature only (:194)
         N = hw * hw
         pool = self.act('head.pool', (B, C))
         F.token_gap_fwd(x3, pool, B, N, C, dt, label='head.pool')
-        Wh = self._w_plain('head.weight', NC, C, 1, 1)
-        self.logits = self.buf('logits', (1, B, NC), torch.float32)
-        F.gemm(pool, Wh, self.logits[0], B, NC, C, dt, bias=P['head.bias'], c_f32=True, label='head.fc')
-        if T:
+        self._linear_head_fwd(pool, 'head.', C, 'head.fc')
+        if self.training:
             Bk = self.bwd
-            self.dlogits = self.buf('dlogits', (1, B, NC))
-            dl = self.dlogits[0]
-            with self._wlane():
-                Bk.wgrad(dl, pool, self.grad('head.weight'), B, NC, C, dt, dbias=self.grad('head.bias'), label='head.wg')
-            dpool = self.tmp('head.dpool', (B, C))
-            Bk.gemm(dl, self.W['head.weight.T'], dpool, B, C, NC, dt, ldb=pad8(NC), label='head.dg')
+            dpool = self._linear_head_bwd(pool, 'head.', C, 'head.dpool')
             seed = self.buf('head.seed', (B * N, C))
             Bk.token_gap_bwd(dpool, seed, B, N, C, dt, label='head.poolb')
             if self.async_wgrad:
@@ -211,10 +169,3 @@ class PiTEngine(MAPPiTEngine):
             Bk.flush('heads.')
             Bk.mark('heads')
             self._build_pit_trunk_backward([None, None, None, seed], K0)
-            if self.async_wgrad:
-                Bk.join_async()
-            Bk.flush('end.')
-        self.prep.flush('prep.')
-
-    def _loss_operands(self):
-        return GAEngine._loss_operands(self)

@@ -12,7 +12,7 @@
                                         ga_se_residual_fwd: relu(res' + r * gate * bn3(conv3)) in one pass (BN-3 and the downsample
                                         BN applied inside it, r = the block's DropPath factors)
   MAPHead ............................. five maps resized to 14 x 14 (stem 112 mode 2 f = 8, layer1 f = 4, layer2 f = 2, layer3
-                                        copy, layer4 mode 3) into one concat -> MAPEngine._build_map_head
+                                        copy, layer4 mode 3) into one concat -> MAPHead._build_map_head
 
 The reference's forward for pool_type='map' calls head(x.mean([-2, -1])) and raises; the engine runs
 head([stem, layer1, layer2, layer3, layer4]), the composition the checkpoint was trained with.
@@ -26,14 +26,12 @@ the multi-scale branch.  DDP bucket marks after the head and after each layer.  
 import torch
 
 from . import ops  # noqa: F401
-from .engine import pad8
-from .engine_map import MAPEngine
+from .engine_base import EngineBase, pad8
+from .engine_map import MAPHead
 from .ops import A_CONV3, A_CONV3S2, A_NEIGH2, C_UNPATCH2
 
 
-class ResNetEngine(MAPEngine):
-    HP = 'head.'
-
+class ResNetEngine(MAPHead, EngineBase):
     def _drop_path_rates(self):
         """map_resnet.py:262-265: block k of 16 (in order) gets drop_path_rate * k / 16"""
         nb, rate = self.cfg['nblock'], self.cfg['drop_path_rate']
@@ -77,12 +75,7 @@ class ResNetEngine(MAPEngine):
         H1 = img // 2
         M1 = B * H1 * H1
         C0 = cfg['stem_ch']
-        self.x8 = self.buf('stem.x8', (B * img * img, 8))
-        self.x_placeholder = torch.zeros(8, device=self.dev)
-        F.nchw3_to_nhwc8(self.x_placeholder, self.x8, B, img, img, dt, label='stem.pack')
-        self.pack_call = len(F.calls) - 1
-        W0 = self.buf('w.stem.0.0', (64, 72))
-        self.prep.convw_pack(P['stem.0.0.weight'], W0, 64, 3, 9, 8, 72, dt, label='prep.stem.0.0')
+        W0 = self._image_pack8_stem('stem.0.0', 64)
         S = self.stem = {}
         S['c0'] = self.act('stem.0.c', (M1, 64))
         S['bn0'], S['a0'] = self._conv_bn_gelu('stem.0.', S['c0'], M1, 64, lambda s, q: F.gemm(
@@ -117,24 +110,11 @@ class ResNetEngine(MAPEngine):
         # ---------------- MultiScale + MAP head ----------------
         Hc = 14
         M4 = B * Hc * Hc
-        srcs = [(x_stem, H1, C0)] + feats
-        ctot = sum(c for _, _, c in srcs)
-        cat = self.act('ms.cat', (M4, ctot))
-        off = 0
-        self.agg_segs = []
-        for src, hw, c in srcs:
-            mode = 0 if hw == Hc else (2 if hw > Hc else 3)
-            F.pool_concat_fwd(src, cat, B, hw, hw, c, Hc, Hc, ctot, off, mode, dt, label=f'agg.{off}')
-            self.agg_segs.append((src, hw, c, mode, off))
-            off += c
+        cat, ctot = self._ms_concat_fwd([(x_stem, H1, C0)] + feats, Hc)
         xh = self._multi_scale_conv_fwd(cat, M4, ctot)
         self._build_map_head(xh, M4, Hc)
         if T:
             self._build_resnet_backward(xh, M4)
-            if self.async_wgrad:
-                self.bwd.join_async()
-            self.bwd.flush('end.')
-        self.prep.flush('prep.')
 
     def _bottleneck_fwd(self, pre, x, H, cin, w, s, has_ds):
         B, T, F, dt, P, Bf = self.B, self.training, self.fwd, self.dt, self.P, self.Bf
@@ -204,13 +184,7 @@ class ResNetEngine(MAPEngine):
     # ------------------------------------------------------------------------------------------
     def _build_resnet_backward(self, xh, M4):
         Bk, B, dt = self.bwd, self.B, self.dt
-        dcat = self._build_head_backward(xh, M4)      # zeroes the arena, marks 'heads'
-        ctot = self.ms['ctot']
-        seeds = []
-        for src, hw, c, mode, off in self.agg_segs:
-            ds = self.buf(f'agg.d{off}', (B * hw * hw, c))
-            Bk.pool_concat_bwd(dcat, None, ds, B, hw, hw, c, 14, 14, ctot, off, mode, dt, label=f'agg.b{off}')
-            seeds.append(ds)
+        seeds = self._ms_concat_bwd(self._build_head_backward(xh, M4))      # (the head backward zeroes the arena, marks 'heads')
         dy = seeds[4]
         for li in range(3, -1, -1):
             for u in reversed(self.layers[li]):
@@ -316,14 +290,3 @@ class ResNetEngine(MAPEngine):
             Bk.gemm(dc1, W1T, dx, Mi, cin, w, dt, ldb=pad8(w), label=pre + 'conv1.dg')
             Bk.subsample2_bwd(dxs, dx, B, H, H, cin, dt, accumulate=True, label=dp + 'subb')
         return dx
-
-    # ------------------------------------------------------------------------------------------
-    def set_input(self, x):
-        x = self._normalize_u8(x)
-        assert x.is_cuda and x.dtype == torch.float32 and tuple(x.shape) == (self.B, 3, self.img, self.img), \
-            f'input must be a float32 CUDA tensor of shape {(self.B, 3, self.img, self.img)}, got {tuple(x.shape)} {x.dtype}'
-        if not x.is_contiguous():
-            x = x.contiguous()
-        self.x_ref = x
-        fn, args, label = self.fwd.calls[self.pack_call]
-        self.fwd.calls[self.pack_call] = (fn, (x.data_ptr(),) + tuple(args[1:]), label)

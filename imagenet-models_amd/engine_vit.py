@@ -1,5 +1,5 @@
 """MAPViTEngine: launch plans of a ViT trunk (timm VisionTransformer: PatchEmbed, cls_token + pos_embed, `Block`s -- the block the
-reference uses through /root/reference/MAP/models/map_pit.py:14,35-44) feeding the MAP head (engine_map.MAPEngine, map.py).
+reference uses through /root/reference/MAP/models/map_pit.py:14,35-44) feeding the MAP head (engine_map.MAPHead, map.py).  ViTBlocks: the builder of that block, which the PiT trunk records too.
 
 The composition (BASELINE configs[4] "MAP-ViT-B/16 @ 384") is builder-defined, modelled on how map_pit.py attaches the head
 (PoolingTransformer.forward_features :185-201: the position-embedded patch tokens and the output of every stage are the feature
@@ -14,34 +14,22 @@ LayerNorm -> fc1 (+GELU) -> fc2 (+ DropPath + residual); weight gradients on the
 import torch
 
 from . import ops  # noqa: F401
-from .engine import pad8
-from .engine_map import MAPEngine
+from .engine_base import EngineBase, pad8
+from .engine_map import MAPHead
 from .ops import ACT_GELU
 
 
-class MAPViTEngine(MAPEngine):
-    def __init__(self, model, batch, training, mode):
-        self._img = model.cfg['img_size']
-        super().__init__(model, batch, training, mode)
+class ViTBlocks:
+    """builder: timm's transformer `Block`, forward and backward, on EngineBase's buffers and plans"""
 
-    def _drop_path_rates(self):
-        """timm VisionTransformer: linspace(0, drop_path_rate, depth); a Block applies it to both branches"""
-        cfg = self.cfg
-        dpr = torch.linspace(0, cfg['drop_path_rate'], cfg['depth']).tolist()
-        out = {}
-        for i in range(cfg['depth']):
-            out[f'blocks.{i}.#1'] = out[f'blocks.{i}.#2'] = dpr[i]
-        return out
-
-    # ------------------------------------------------------------------------------------------
     def _vit_block_fwd(self, pre, x, M, C, heads, Ntok):
-        """inside a forward chain (GAEngine._chains: the trunk recorded once per batch part, each part on its own lane) the launches
+        """inside a forward chain (EngineBase._chains: the trunk recorded once per batch part, each part on its own lane) the launches
         cover the chain's rows of the same full-batch buffers; weight preparation and the backward's attention descriptor are recorded
         by the first pass only"""
         F, dt, B, P, T = self.fwd, self.dt, self.B, self.P, self.training
         (lane, r0, r1, b0, b1), = self._fsplits(Ntok)
         first = pre not in self.blocks
-        if getattr(self, '_chain', None) is not None:
+        if self._chain is not None:
             F.lane = lane
         n = r1 - r0
         dp1, dp2 = self.dp_scale.get(pre + '#1'), self.dp_scale.get(pre + '#2')
@@ -161,11 +149,21 @@ class MAPViTEngine(MAPEngine):
         if side:
             Bk.async_mark(f'blk{self._bwd_seq}')
 
-    # ------------------------------------------------------------------------------------------
+
+class MAPViTEngine(ViTBlocks, MAPHead, EngineBase):
+    def _drop_path_rates(self):
+        """timm VisionTransformer: linspace(0, drop_path_rate, depth); a Block applies it to both branches"""
+        cfg = self.cfg
+        dpr = torch.linspace(0, cfg['drop_path_rate'], cfg['depth']).tolist()
+        out = {}
+        for i in range(cfg['depth']):
+            out[f'blocks.{i}.#1'] = out[f'blocks.{i}.#2'] = dpr[i]
+        return out
+
     def _build(self):
         cfg = self.cfg
         B, T, F, dt, P = self.B, self.training, self.fwd, self.dt, self.P
-        self.img = img = self._img
+        img = self.img
         C, depth, heads, ps = cfg['embed_dim'], cfg['depth'], cfg['vit_heads'], cfg['patch_size']
         gw = img // ps
         Np, Ntok = gw * gw, gw * gw + 1
@@ -176,8 +174,8 @@ class MAPViTEngine(MAPEngine):
         # ---------------- patch embedding + class token + position embedding ----------------
         self.x_placeholder = torch.zeros(B, 3, img, img, device=self.dev)
         patches = self.patches = self.act('patch.cols', (Mp, K0))
+        self.input_call = len(F.calls)
         F.patchify(self.x_placeholder, patches, ps, dt, label='patch.pack')
-        self.pack_call = len(F.calls) - 1
         Wpe = self._w_plain('patch_embed.proj.weight', C, K0, 1, 1, need_T=False)
         tok = self.tmp('patch.tok', (Mp, C))
         x0 = self.buf('embed.x0', (M, C))
@@ -210,22 +208,13 @@ class MAPViTEngine(MAPEngine):
         F.lane = 0
         self.x_last = x
         # ---------------- MultiScale: every map (gw x gw) reduced to gw/2 x gw/2, concat, conv1x1 + BN + GELU ----------------
-        Hc = self.Hc = gw // 2
+        Hc = gw // 2
         M4 = B * Hc * Hc
-        ctot = C * len(feats)
-        cat = self.act('ms.cat', (M4, ctot))
-        self.agg_segs = []
-        for j, fm in enumerate(feats):
-            F.pool_concat_fwd(fm, cat, B, gw, gw, C, Hc, Hc, ctot, j * C, 2, dt, label=f'agg.{j}')
-            self.agg_segs.append((fm, gw, C, 2, j * C))
+        cat, ctot = self._ms_concat_fwd([(fm, gw, C) for fm in feats], Hc, labels=[f'agg.{j}' for j in range(len(feats))])
         xh = self._multi_scale_conv_fwd(cat, M4, ctot)
         self._build_map_head(xh, M4, Hc)
         if T:
             self._build_vit_backward(xh, M4, feats, B, Np, Ntok, C, M, Mp, K0)
-            if self.async_wgrad:
-                self.bwd.join_async()
-            self.bwd.flush('end.')
-        self.prep.flush('prep.')
 
     def _tokens_to_map(self, x, name, B, Np, Ntok, C):
         """drop the class token: rows 1.. of every image -> [B*Np, C] (the images of the current forward chain)"""
@@ -237,13 +226,7 @@ class MAPViTEngine(MAPEngine):
     def _build_vit_backward(self, xh, M4, feats, B, Np, Ntok, C, M, Mp, K0):
         Bk, dt, P, cfg = self.bwd, self.dt, self.P, self.cfg
         depth, gw = cfg['depth'], self.img // cfg['patch_size']
-        dcat = self._build_head_backward(xh, M4)
-        ctot = self.ms['ctot']
-        seeds = []
-        for fm, hw, c, mode, off in self.agg_segs:
-            ds = self.buf(f'agg.d{off}', (B * hw * hw, c))
-            Bk.pool_concat_bwd(dcat, None, ds, B, hw, hw, c, self.Hc, self.Hc, ctot, off, mode, dt, label=f'agg.b{off}')
-            seeds.append(ds)
+        seeds = self._ms_concat_bwd(self._build_head_backward(xh, M4))
         # gradient of the token sequence, three rotating buffers (the asynchronous weight gradients read dx of the block before)
         dxs = [self.buf(f'vit.dx{j}', (M, C)) for j in range(3)]
         cur = 0
@@ -273,13 +256,3 @@ class MAPViTEngine(MAPEngine):
         with self._wlane():
             Bk.wgrad(dtok, self.patches, self.grad('patch_embed.proj.weight'), Mp, C, K0, dt, dbias=self.grad('patch_embed.proj.bias'),
                      label='patch.wg')
-
-    def set_input(self, x):
-        x = self._normalize_u8(x)
-        assert x.is_cuda and x.dtype == torch.float32 and tuple(x.shape) == (self.B, 3, self.img, self.img), \
-            f'input must be a float32 CUDA tensor of shape {(self.B, 3, self.img, self.img)}, got {tuple(x.shape)} {x.dtype}'
-        if not x.is_contiguous():
-            x = x.contiguous()
-        self.x_ref = x
-        fn, args, label = self.fwd.calls[self.pack_call]
-        self.fwd.calls[self.pack_call] = (fn, (x.data_ptr(),) + tuple(args[1:]), label)

@@ -23,8 +23,8 @@ def set_schedule(monkeypatch, serial):
 
 def record_bn_sums(monkeypatch):
     """every engine built after this call keeps [(BatchNorm prefix, its s / q pool slices)] in creation order (= forward order)"""
-    from imagenet_models_amd.engine import GAEngine
-    orig = GAEngine._bn_bufs
+    from imagenet_models_amd.engine_base import EngineBase
+    orig = EngineBase._bn_bufs
 
     def rec(self, pre, C, zero=False):
         d = orig(self, pre, C, zero=zero)
@@ -32,7 +32,7 @@ def record_bn_sums(monkeypatch):
             self._bn_record = []
         self._bn_record.append((pre, d))
         return d
-    monkeypatch.setattr(GAEngine, '_bn_bufs', rec)
+    monkeypatch.setattr(EngineBase, '_bn_bufs', rec)
 
 
 def bn_sums(model):

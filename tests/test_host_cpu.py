@@ -235,6 +235,37 @@ def test_drop_path_schedule_matches_reference():
     assert abs(rates['gram_layer.3.blocks.0.'] - ref[4][0]) < 1e-7 and rates['stages.4.'] == pytest.approx(0.2)
 
 
+def test_engines_compose_builders_over_one_base():
+    """every engine family is engine_base.EngineBase plus the builders it runs: no family carries another family's head, and no
+    method name means two things inside one engine (same name in two classes of an MRO -> same parameter list; against the base
+    only its declared hooks _build / _drop_path_rates are compared)"""
+    import inspect
+    from imagenet_models_amd.engine import GAEngine
+    from imagenet_models_amd.engine_base import EngineBase
+    from imagenet_models_amd.engine_convnext import ConvNeXtEngine
+    from imagenet_models_amd.engine_cswin import CSWinEngine
+    from imagenet_models_amd.engine_map import MAPEngine
+    from imagenet_models_amd.engine_mobilenet import MobileNetEngine
+    from imagenet_models_amd.engine_pit import MAPPiTEngine, PiTEngine
+    from imagenet_models_amd.engine_resnet import ResNetEngine
+    from imagenet_models_amd.engine_vit import MAPViTEngine
+    families = [MAPEngine, MAPViTEngine, MAPPiTEngine, PiTEngine, ResNetEngine, MobileNetEngine, ConvNeXtEngine, CSWinEngine]
+    for E in families:
+        assert issubclass(E, EngineBase), E
+        assert hasattr(E, '_build_heads') == (E is CSWinEngine), E
+    assert not hasattr(PiTEngine, '_build_map_head') and not hasattr(ConvNeXtEngine, '_build_map_head')
+    for E in families + [GAEngine]:
+        assert E.__mro__[-2] is EngineBase, E       # the base comes last
+        seen = {}
+        for cls in E.__mro__[:-1]:
+            for name, f in vars(cls).items():
+                f = getattr(f, '__func__', f)       # staticmethod
+                if not inspect.isfunction(f) or (cls is EngineBase and name not in ('_build', '_drop_path_rates')):
+                    continue
+                sig = str(inspect.signature(f))
+                assert seen.setdefault(name, (cls, sig))[1] == sig, (E.__name__, name, seen[name], cls, sig)
+
+
 def test_load_timm_layout_checkpoint_with_args_namespace(tmp_path):
     """timm CheckpointSaver files (GA/train.py:649-651: args=args) hold an argparse.Namespace, 'module.'-prefixed keys when
     saved from DDP, and state_dict_ema: load_checkpoint must read them under weights_only=True"""
