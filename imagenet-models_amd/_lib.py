@@ -142,6 +142,8 @@ _SIGS = {
     'ga_subsample2_fwd': ([vp, vp, i32, i32, i32, i32, i32, vp], i32),
     'ga_subsample2_bwd': ([vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
     'ga_wgrad_workspace': ([C.POINTER(WgradDesc)], C.c_size_t),
+    'ga_gemm_form': ([C.POINTER(GemmDesc), C.c_char_p, C.c_size_t], i32),
+    'ga_wgrad_form': ([C.POINTER(WgradDesc), C.c_char_p, C.c_size_t], i32),
     'ga_layernorm_fwd': ([vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp], i32),
     'ga_layernorm_bwd': ([vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp], i32),
     'ga_layernorm_bwd_dp': ([vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, i64, i32, vp], i32),

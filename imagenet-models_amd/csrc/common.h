@@ -207,14 +207,15 @@ template <int G> __device__ __forceinline__ float group_sum(float v) {
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
-// conv3.hip: the direct 3 x 3 / 64-channel form of ga_gemm's GA_A_CONV3 product; returns 1 if it took the launch
-int ga_conv3_c64_try(const ga_gemm_desc* d, hipStream_t s);
-// ... and of the GA_A_CONV3S2 product of the 3 -> 64-channel first convolution on the NHWC8 image
-int ga_conv0_c8_try(const ga_gemm_desc* d, hipStream_t s);
-size_t ga_conv3_c64_wgrad_workspace(const ga_wgrad_desc* d);
-int ga_conv3_c64_wgrad_try(const ga_wgrad_desc* d, hipStream_t s);
-int ga_conv3s2_c64_wgrad_try(const ga_wgrad_desc* d, hipStream_t s);
-int ga_conv0_c8_wgrad_try(const ga_wgrad_desc* d, hipStream_t s);
-// ... and the direct form of ga_wgrad's GA_A_STEM4_NCHW product (ConvNeXt stem): bytes of per-workgroup partials / the launch
-size_t ga_stem4_wgrad_workspace(const ga_wgrad_desc* d);
-int ga_stem4_wgrad_try(const ga_wgrad_desc* d, hipStream_t s);
+// number of compute units of the current device, asked once (runtime.hip); 256 (the MI355X's) when there is no device
+int ga_num_cus();
+
+// conv3.hip: launches of the direct forms that gemm_select.h names (their eligibility predicates are declared there).
+// ga_gemm's GA_A_CONV3 product at 64 -> 64 channels and its GA_A_CONV3S2 product of the 3 (8) -> 64-channel first convolution;
+// ga_wgrad's counterparts and its GA_A_STEM4_NCHW product (ConvNeXt stem).  The int ones return 0 when nothing was launched.
+int ga_conv3_c64_launch(const ga_gemm_desc* d, hipStream_t s);
+void ga_conv0_c8_launch(const ga_gemm_desc* d, hipStream_t s);
+int ga_conv3_c64_wgrad_launch(const ga_wgrad_desc* d, int wgs, hipStream_t s);
+int ga_conv3s2_c64_wgrad_launch(const ga_wgrad_desc* d, int wgs, hipStream_t s);
+int ga_conv0_c8_wgrad_launch(const ga_wgrad_desc* d, int wgs, hipStream_t s);
+int ga_stem4_wgrad_launch(const ga_wgrad_desc* d, int wgs, hipStream_t s);

@@ -13,6 +13,7 @@
 //   pixel; results go through a per-wave staging piece to 16-byte NHWC stores.
 //   Bound: LDS reads (6 ds_read_b128 per 8 MFMAs, one workgroup of 133 KiB per CU).
 #include "common.h"
+#include "gemm_select.h"      // declares the eligibility predicates defined below
 
 namespace {
 
@@ -1020,8 +1021,7 @@ extern "C" int ga_stem4_ln_fwd(const float* x, const void* W, int64_t ldw, const
     GA_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(pre) |
                  reinterpret_cast<uintptr_t>(y)) & 15) == 0, "ga_stem4_ln_fwd: operands must be 16-byte aligned");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    int cus = 256;
-    ga_device_info(&cus, nullptr, nullptr);
+    const int cus = ga_num_cus();
     const long ngroups = ((long)B * (H / 4) * (W_ / 4) + 15) / 16;
     const int grid = (int)std::max<long>(1, std::min<long>((ngroups + 3) / 4, (long)cus * 8));
     if (C == 96)
@@ -1033,9 +1033,8 @@ extern "C" int ga_stem4_ln_fwd(const float* x, const void* W, int64_t ldw, const
     return ga_check_launch("ga_stem4_ln_fwd");
 }
 
-// ga_gemm's GA_A_CONV3S2 product for the 3 -> 64-channel first convolution on the NHWC8 image: returns 1 if it took the launch
-int ga_conv0_c8_try(const ga_gemm_desc* d, hipStream_t s) {
-    if (!GA_KNOB("CONV0_DIRECT", 1)) return 0;
+// ga_gemm's GA_A_CONV3S2 product for the 3 -> 64-channel first convolution on the NHWC8 image: does the direct kernel take it
+bool ga_conv0_c8_eligible(const ga_gemm_desc* d) {
     if (d->dtype != GA_BF16 || d->a_kind != GA_A_CONV3S2 || d->a_C != 8 || d->N != 64 || d->K != 72 || d->batch != 1) return 0;
     if (d->c_kind != GA_C_PLAIN || d->c_f32 || d->ldc != 64 || d->bias || d->R || d->H || d->C2 || d->rowscale || d->colsum || d->colsumsq ||
         d->act != GA_ACT_NONE || d->a_act != GA_ACT_NONE || d->relu_after || d->alpha != 1.0f)
@@ -1046,35 +1045,37 @@ int ga_conv0_c8_try(const ga_gemm_desc* d, hipStream_t s) {
     const long ohw = (long)(d->a_H / 2) * (d->a_W / 2);
     if (d->M % ohw != 0) return 0;
     const long nimg = d->M / ohw;
-    const long in_bytes = nimg * d->a_H * d->a_W * 16, out_bytes = d->M * 128;
-    if (in_bytes >= (1L << 31) || out_bytes >= (1L << 31)) return 0;
-    int cus = 256;
-    ga_device_info(&cus, nullptr, nullptr);
+    const long in_bytes = nimg * d->a_H * d->a_W * 16, out_bytes = d->M * 128L;
+    return in_bytes < (1L << 31) && out_bytes < (1L << 31);
+}
+void ga_conv0_c8_launch(const ga_gemm_desc* d, hipStream_t s) {
+    const long nimg = d->M / ((long)(d->a_H / 2) * (d->a_W / 2));
+    const long in_bytes = nimg * d->a_H * d->a_W * 16, out_bytes = d->M * 128L;
+    const int cus = ga_num_cus();
     const long ngroups = nimg * (d->a_H / 2) * ((d->a_W / 2 + 15) / 16);
     const int grid = (int)std::max<long>(1, std::min<long>((ngroups + 4 * C0_NG - 1) / (4 * C0_NG), (long)cus * 8));
     hipLaunchKernelGGL(conv0_c8_kernel, dim3(grid), dim3(256), 0, s, (const bf16_t*)d->A, (const bf16_t*)d->B, (long)d->ldb, (bf16_t*)d->C,
                        (int)nimg, d->a_H, d->a_W, (unsigned)in_bytes, (unsigned)out_bytes);
-    return 1;
 }
 
-// ga_gemm's GA_A_CONV3 product, plain epilogue, bf16, 64 input channels, N = 64, maps of 8 x 16 tiles: returns 1 if it took the launch
-int ga_conv3_c64_try(const ga_gemm_desc* d, hipStream_t s) {
-    if (!GA_KNOB("CONV3_DIRECT", 1)) return 0;
+// ga_gemm's GA_A_CONV3 product, plain epilogue, bf16, 64 input channels, N = 64, maps of 8 x 16 tiles: does the direct kernel take it
+bool ga_conv3_c64_eligible(const ga_gemm_desc* d) {
     if (d->dtype != GA_BF16 || d->a_kind != GA_A_CONV3 || d->a_C != 64 || d->N != 64 || d->K != 576 || d->batch != 1) return 0;
     if (d->c_kind != GA_C_PLAIN || d->c_f32 || d->ldc != 64 || d->bias || d->R || d->H || d->C2 || d->rowscale || d->colsum || d->colsumsq ||
         d->act != GA_ACT_NONE || d->a_act != GA_ACT_NONE || d->relu_after || d->alpha != 1.0f)
         return 0;
     if (d->a_H % TH != 0 || d->a_W % TW != 0 || d->ldb % 8 != 0) return 0;
     const long hw = (long)d->a_H * d->a_W;
-    if (d->M % hw != 0) return 0;
-    const long nimg = d->M / hw;
-    const long bytes = d->M * 128;
-    if (bytes >= (1L << 31)) return 0;
+    return d->M % hw == 0 && d->M * 128L < (1L << 31);
+}
+// ... and its launch: 0 (nothing launched) when the kernel's LDS cannot be reserved, the gather GEMM then takes the product
+int ga_conv3_c64_launch(const ga_gemm_desc* d, hipStream_t s) {
+    const long nimg = d->M / ((long)d->a_H * d->a_W);
+    const long bytes = d->M * 128L;
     static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_c64_kernel),
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL) == hipSuccess;
     if (!attr_ok) return 0;
-    int cus = 256;
-    ga_device_info(&cus, nullptr, nullptr);
+    const int cus = ga_num_cus();
     const long ntiles = nimg * (d->a_H / TH) * (d->a_W / TW);
     const int grid = (int)std::min<long>(ntiles, cus);
     hipLaunchKernelGGL(conv3_c64_kernel, dim3(grid), dim3(256), LDS_TOTAL, s, (const bf16_t*)d->A, (const bf16_t*)d->B, (long)d->ldb,
@@ -1084,69 +1085,50 @@ int ga_conv3_c64_try(const ga_gemm_desc* d, hipStream_t s) {
 
 // ga_wgrad's GA_A_CONV3 product for the same layer (bf16, 64 -> 64 channels, accumulate into dW, no bias): workgroups / bytes of
 // partial sums it needs (0: does not apply)
-static int conv3_wgrad_wgs(const ga_wgrad_desc* d) {
-    if (!GA_KNOB("CONV3_DIRECT", 1)) return 0;
+int ga_conv3_c64_wgrad_wgs(const ga_wgrad_desc* d, int cus) {
     if (d->dtype != GA_BF16 || d->x_kind != GA_A_CONV3 || d->x_C != 64 || d->N != 64 || d->K != 576 || d->batch != 1 || d->dbias ||
         d->x_act != GA_ACT_NONE || d->ldy != 64 || !d->accumulate)
         return 0;
     if (d->x_H % TH != 0 || d->x_W % TW != 0 || (long)d->M % ((long)d->x_H * d->x_W) != 0 || (long)d->M * 128 >= (1L << 31)) return 0;
-    int cus = 256;
-    ga_device_info(&cus, nullptr, nullptr);
     const long ntiles = (long)d->M / (TH * TW);
     return (int)std::min<long>(ntiles, cus);
 }
 // ... and for the stride-2 convolution (GA_A_CONV3S2: x_H x x_W is the INPUT map, M the output pixels)
-static int conv3s2_wgrad_wgs(const ga_wgrad_desc* d) {
-    if (!GA_KNOB("CONV3_DIRECT", 1)) return 0;
+int ga_conv3s2_c64_wgrad_wgs(const ga_wgrad_desc* d, int cus) {
     if (d->dtype != GA_BF16 || d->x_kind != GA_A_CONV3S2 || d->x_C != 64 || d->N != 64 || d->K != 576 || d->batch != 1 || d->dbias ||
         d->x_act != GA_ACT_NONE || d->ldy != 64 || !d->accumulate)
         return 0;
     if (d->x_H % (2 * T2) != 0 || d->x_W % (2 * T2) != 0) return 0;
     const long ohw = (long)(d->x_H / 2) * (d->x_W / 2);
     if ((long)d->M % ohw != 0 || (long)d->M * 4 * 128 >= (1L << 31)) return 0;
-    int cus = 256;
-    ga_device_info(&cus, nullptr, nullptr);
     const long ntiles = (long)d->M / (T2 * T2);
     return (int)std::min<long>(ntiles, cus);
 }
 // ... and for the first convolution (GA_A_CONV3S2 on the 8-channel image copy)
-static int conv0_wgrad_wgs(const ga_wgrad_desc* d) {
-    if (!GA_KNOB("CONV0_DIRECT", 1)) return 0;
+int ga_conv0_c8_wgrad_wgs(const ga_wgrad_desc* d, int cus) {
     if (d->dtype != GA_BF16 || d->x_kind != GA_A_CONV3S2 || d->x_C != 8 || d->N != 64 || d->K != 72 || d->batch != 1 || d->dbias ||
         d->x_act != GA_ACT_NONE || d->ldy != 64 || !d->accumulate)
         return 0;
     if (d->x_H % (2 * TH) != 0 || d->x_W % (2 * TW) != 0) return 0;
     const long ohw = (long)(d->x_H / 2) * (d->x_W / 2);
     if ((long)d->M % ohw != 0 || (long)d->M * 128 >= (1L << 31)) return 0;
-    int cus = 256;
-    ga_device_info(&cus, nullptr, nullptr);
     const long ntiles = (long)d->M / (TH * TW);
     return (int)std::min<long>(ntiles, 2L * cus);
 }
-size_t ga_conv3_c64_wgrad_workspace(const ga_wgrad_desc* d) {
-    if (d->x_kind == GA_A_CONV3S2 && d->x_C == 8) return (size_t)conv0_wgrad_wgs(d) * 64 * 72 * sizeof(float);
-    const int wgs = d->x_kind == GA_A_CONV3S2 ? conv3s2_wgrad_wgs(d) : conv3_wgrad_wgs(d);
-    return (size_t)wgs * 64 * 576 * sizeof(float);
-}
 
 // ga_wgrad's GA_A_STEM4_NCHW product (bf16, N = 96 / 128, K = 48): workgroups of the direct form (0: does not apply)
-static int stem4_wgrad_wgs(const ga_wgrad_desc* d) {
-    if (!GA_KNOB("STEM4_WGRAD_DIRECT", 1)) return 0;
+int ga_stem4_wgrad_wgs(const ga_wgrad_desc* d, int cus) {
     if (d->dtype != GA_BF16 || d->x_kind != GA_A_STEM4_NCHW || (d->N != 96 && d->N != 128) || d->K != 48 || d->x_C != 3 || d->batch != 1 ||
         d->x_act != GA_ACT_NONE || d->ldy != d->N)
         return 0;
     if (d->x_H <= 0 || d->x_W <= 0 || d->x_H % 4 != 0 || d->x_W % 4 != 0) return 0;
     const long ohw = (long)(d->x_H / 4) * (d->x_W / 4);
     if ((long)d->M % ohw != 0 || (long)d->M * 48 >= (1L << 31)) return 0;
-    int cus = 256;
-    ga_device_info(&cus, nullptr, nullptr);
     return (int)std::min<long>(((long)d->M + 127) / 128, 2L * cus);
 }
-size_t ga_stem4_wgrad_workspace(const ga_wgrad_desc* d) { return (size_t)stem4_wgrad_wgs(d) * d->N * 49 * sizeof(float); }
-
-int ga_stem4_wgrad_try(const ga_wgrad_desc* d, hipStream_t s) {
-    const int wgs = stem4_wgrad_wgs(d);
-    if (!wgs || !d->workspace || (size_t)d->ws_bytes < (size_t)wgs * d->N * 49 * sizeof(float)) return 0;
+// the launches of the direct weight-gradient kernels, wgs workgroups with their partial sums in d->workspace (ga_wgrad has checked
+// its size): 0 (nothing launched) when the kernel's LDS cannot be reserved
+int ga_stem4_wgrad_launch(const ga_wgrad_desc* d, int wgs, hipStream_t s) {
     float* part = reinterpret_cast<float*>(d->workspace);
     const int want_bias = d->dbias != nullptr;
     if (d->N == 96)
@@ -1160,9 +1142,7 @@ int ga_stem4_wgrad_try(const ga_wgrad_desc* d, hipStream_t s) {
     return 1;
 }
 
-int ga_conv0_c8_wgrad_try(const ga_wgrad_desc* d, hipStream_t s) {
-    const int wgs = conv0_wgrad_wgs(d);
-    if (!wgs || !d->workspace || (size_t)d->ws_bytes < (size_t)wgs * 64 * 72 * sizeof(float)) return 0;
+int ga_conv0_c8_wgrad_launch(const ga_wgrad_desc* d, int wgs, hipStream_t s) {
     static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(conv0_c8_wgrad_kernel),
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, WG_LDS0) == hipSuccess;
     if (!attr_ok) return 0;
@@ -1175,9 +1155,7 @@ int ga_conv0_c8_wgrad_try(const ga_wgrad_desc* d, hipStream_t s) {
     return 1;
 }
 
-int ga_conv3s2_c64_wgrad_try(const ga_wgrad_desc* d, hipStream_t s) {
-    const int wgs = conv3s2_wgrad_wgs(d);
-    if (!wgs || !d->workspace || (size_t)d->ws_bytes < (size_t)wgs * 64 * 576 * sizeof(float)) return 0;
+int ga_conv3s2_c64_wgrad_launch(const ga_wgrad_desc* d, int wgs, hipStream_t s) {
     static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3s2_c64_wgrad_kernel),
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, WG_LDS2) == hipSuccess;
     if (!attr_ok) return 0;
@@ -1190,9 +1168,7 @@ int ga_conv3s2_c64_wgrad_try(const ga_wgrad_desc* d, hipStream_t s) {
     return 1;
 }
 
-int ga_conv3_c64_wgrad_try(const ga_wgrad_desc* d, hipStream_t s) {
-    const int wgs = conv3_wgrad_wgs(d);
-    if (!wgs || !d->workspace || (size_t)d->ws_bytes < (size_t)wgs * 64 * 576 * sizeof(float)) return 0;
+int ga_conv3_c64_wgrad_launch(const ga_wgrad_desc* d, int wgs, hipStream_t s) {
     static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_c64_wgrad_kernel),
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, WG_LDS) == hipSuccess;
     if (!attr_ok) return 0;

@@ -15,15 +15,6 @@
 
 namespace {
 
-int num_cus() {
-    static int n = [] {
-        int c = 256;
-        ga_device_info(&c, nullptr, nullptr);
-        return c;
-    }();
-    return n;
-}
-
 constexpr int kCSF = 32;  // channels per slice, forward / backward-data kernel (LDS 32 KiB -> 4-5 workgroups per CU)
 constexpr int kCSW = 64;  // channels per slice, backward-weight kernel (224 of 256 threads hold accumulators)
 constexpr int kCG = 4;    // channels per work item
@@ -1204,7 +1195,7 @@ int launch_dwconv_rs_t(const void* x, const float* w49, const float* bias, const
     // still gives every SIMD its two waves (measured at 256 x 56 x 56 x 96: R = 56 0.101 ms, 28 0.118, 14 0.130)
     int R = GA_KNOB("DW_RS_ROWS", 0);
     if (R <= 0 || R % 7 != 0 || H % R != 0) {
-        const long slots = 8L * num_cus();
+        const long slots = 8L * ga_num_cus();
         R = 7;
         for (int d = 1; d <= H / 7; ++d) {
             if ((H / 7) % d != 0) continue;
@@ -1454,7 +1445,7 @@ inline bool dww_rs_geometry(int B, int H, int W, int C, int* R_out, int* wpu_out
     if (C % 8 != 0 || H % 7 != 0 || (long)B * H * W * C * 2 >= (1L << 31)) return false;
     const int nstrips = cdiv(W, DWW::TW);
     const int wpu = cdiv(nstrips * (C / 2), 64);
-    const int nbw = std::max(1, 2 * num_cus() / wpu);          // two workgroups per CU
+    const int nbw = std::max(1, 2 * ga_num_cus() / wpu);          // two workgroups per CU
     // rows per segment: the longest march that still gives each of the 4 * nbw waves of a lane map about two units
     int R = GA_KNOB("DWW_RS_ROWS", 0);
     if (R <= 0 || R % 7 != 0 || H % R != 0) {
@@ -1517,18 +1508,18 @@ int launch_dwconv(const void* x, const float* w49, const float* bias, const void
             const int sl = cdiv(C, 64);
             const bool big = H % 14 == 0 && W % 14 == 0;
             const long ntiles = big ? (long)B * (H / 14) * (W / 14) : (long)B * cdiv(H, 7) * cdiv(W, 7);
-            const int gx = (int)std::min<long>(ntiles, std::max(1, (big ? 2 : 4) * num_cus() / sl));
+            const int gx = (int)std::min<long>(ntiles, std::max(1, (big ? 2 : 4) * ga_num_cus() / sl));
             const int use_mfma = GA_KNOB("DW_MFMA", 1);     // 0: never, 1: heuristic (default), 2: every 14 x 14-tiled launch
             // the MFMA form pays a long prologue (Toeplitz fragments) per workgroup: ahead of the dot2 form only when
             // a workgroup walks many tiles (56 x 56 maps, also as half batches: 0.169 vs 0.192 ms; 28 x 28 and 14 x 14:
             // 5-10 % behind)
-            const bool many = H * W >= 56 * 56 && ntiles * cdiv(C, DWM::CS) >= 16L * num_cus();
+            const bool many = H * W >= 56 * 56 && ntiles * cdiv(C, DWM::CS) >= 16L * ga_num_cus();
             if (big && (use_mfma == 2 || (use_mfma == 1 && many))) {
                 const int slm = cdiv(C, DWM::CS);
                 // grid.x a multiple of 8: workgroup (x, y) then sits on XCD x % 8 for every slice y, so the 32-channel slices of
                 // one tile (64 of the 128 bytes of every line each) share one L2 instead of fetching the line once per slice
                 const int xcd8 = GA_KNOB("DW_XCD8", 1);
-                int gxm = (int)std::min<long>(ntiles, std::max(1, num_cus() / slm));
+                int gxm = (int)std::min<long>(ntiles, std::max(1, ga_num_cus() / slm));
                 if (xcd8 && gxm >= 16) gxm = gxm / 8 * 8;
                 hipLaunchKernelGGL(dwconv7_mfma_kernel, dim3(gxm, slm), dim3(DWM::NT), DWM::LDS, s, (const bf16_t*)x, w49, bias,
                                    (const bf16_t*)res, (bf16_t*)y, B, H, W, C, flip, (bf16_t*)y2, y2scale);
@@ -1572,7 +1563,7 @@ void dwconv_wgrad_geometry(int B, int H, int W, int C, bool bf16, int* gx_out, i
     const bool big = H % 14 == 0 && W % 14 == 0;
     const long ntiles = big ? (long)B * (H / 14) * (W / 14) : (long)B * cdiv(H, 7) * cdiv(W, 7);
     const bool dot2 = bf16 && C % 8 == 0;   // dot2 form: 89 KB of LDS at 14x14 -> one workgroup per CU
-    const int gx = (int)std::min<long>(ntiles, std::max(1, (big ? (dot2 ? 1 : 2) : 4) * num_cus() / slices));
+    const int gx = (int)std::min<long>(ntiles, std::max(1, (big ? (dot2 ? 1 : 2) : 4) * ga_num_cus() / slices));
     *gx_out = gx;
     *nparts_out = gx * (big ? 2 : 1);          // one partial per (workgroup, group of 7 output rows)
 }

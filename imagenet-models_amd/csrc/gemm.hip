@@ -19,17 +19,9 @@
 #include <algorithm>
 #include <type_traits>
 #include "common.h"
+#include "gemm_select.h"
 
 namespace {
-
-int num_cus() {
-    static int n = [] {
-        int c = 256;
-        ga_device_info(&c, nullptr, nullptr);
-        return c;
-    }();
-    return n;
-}
 
 constexpr int kThreads = 256;
 constexpr int kRowBytes = 128;          // bytes of K per LDS row (NT kernel)
@@ -271,7 +263,7 @@ template <int TNW, int NWM> struct NTCfg {
 // ~14k instructions, most of them never executed by the hot launches, and thrashes the instruction cache):
 //   0 plain (bias, optional column sums)      1 fc1: bias + GELU, second output GELU'
 //   2 fc2: bias (+ DropPath row scale) + residual      3 dgrad2: multiply by the stored GELU' (+ column sums)
-enum { EPI_GENERIC = -1, EPI_PLAIN = 0, EPI_FC1 = 1, EPI_FC2 = 2, EPI_DG2 = 3 };
+using gasel::EPI_GENERIC, gasel::EPI_PLAIN, gasel::EPI_FC1, gasel::EPI_FC2, gasel::EPI_DG2;   // gemm_select.h
 
 // DMA (bf16, plain A): the K slabs are brought in by LDS-DMA (glds16) into a 2-slot ring that sits BEHIND the fp32
 // staging area of the epilogue, one barrier per slab; the stream of slabs runs across tile boundaries, so the first
@@ -2006,43 +1998,29 @@ __global__ __launch_bounds__(256) void tn2_reduce_kernel(const float* __restrict
     }
 }
 
-// the wide form needs whole 32-row stages, plain bf16 operands, and an output that is accumulated into (so that it
-// may choose its own row split); it pays once the reduction is long enough to amortise the 256 x 256 tile
-// GA_A_PATCH2 operands (TN2_PATCH2, default 1): NHWC map of even sides with C % 8 == 0, K == 4 C, byte offsets < 2^31
-bool tn2_eligible(const ga_wgrad_desc* d) {
-    if (!(GA_KNOB("TN2", 1) && d->dtype == GA_BF16 && d->x_act == GA_ACT_NONE && d->M % 32 == 0 && d->M >= 8192 &&
-          (d->accumulate || d->split_m > 1) && (long)d->M * d->ldy < (1L << 31)))                    // 32-bit byte offsets
-        return false;
-    if (d->x_kind == GA_A_PLAIN) return (long)d->M * d->ldx < (1L << 31);
-    if (d->x_kind == GA_A_PATCH2)
-        return GA_KNOB("TN2_PATCH2", 1) && d->x_C > 0 && d->x_C % 8 == 0 && d->K == 4 * d->x_C && d->x_H > 0 && d->x_W > 0 &&
-               d->x_H % 2 == 0 && d->x_W % 2 == 0 && d->M % ((long)(d->x_H / 2) * (d->x_W / 2)) == 0 &&
-               8L * d->M * d->x_C < (1L << 31);
-    return false;
+using namespace gasel;      // the selection: gemm_select.h
+
+// the knob table's values of the knobs the selection reads
+Knobs current_knobs() {
+    Knobs k;
+#define GA_SEL_KNOB(NAME) k.NAME = GA_KNOB(#NAME, Knobs{}.NAME)
+    GA_SEL_KNOB(NT_R3); GA_SEL_KNOB(NT_R3_NEIGH2); GA_SEL_KNOB(NT_R3_CONV3S2); GA_SEL_KNOB(NT_PP); GA_SEL_KNOB(NT_PP_MINK);
+    GA_SEL_KNOB(NT_BIG); GA_SEL_KNOB(NT_DMA); GA_SEL_KNOB(NT_DMA2); GA_SEL_KNOB(NT_DMA2_MINK); GA_SEL_KNOB(NT_T256);
+    GA_SEL_KNOB(TN2); GA_SEL_KNOB(TN2_PATCH2); GA_SEL_KNOB(TN2_WGS); GA_SEL_KNOB(TN2_PART_MIN);
+    GA_SEL_KNOB(CONV3_DIRECT); GA_SEL_KNOB(CONV0_DIRECT); GA_SEL_KNOB(STEM4_WGRAD_DIRECT);
+#undef GA_SEL_KNOB
+    return k;
 }
 
-// row split of the wide form and the bytes of partial-tile workspace it wants (0: combine with atomics)
-size_t tn2_plan(const ga_wgrad_desc* d, int* split_out) {
-    const int tiles = cdiv(d->N, 256) * cdiv(d->K, 256) * d->batch;
-    const int stages = d->M / 32;
-    const int wg_budget = GA_KNOB("TN2_WGS", 0);
-    // 3/4 of the CUs: in the train step these launches share the chip with the dgrad chain (asynchronous lane), and
-    // fewer row splits mean fewer partial tiles to write and reduce (same-box A/B: 192 vs 256 workgroups -0.13 ms/step)
-    const int cus = wg_budget > 0 ? wg_budget : num_cus() * 3 / 4;
-    int split = std::max(1, std::min(stages / 8, cus / tiles));               // one workgroup per CU
-    split = cdiv(stages, cdiv(stages, split));                                // no empty row range
-    *split_out = split;
-    const long nk = (long)d->N * d->K;
-    const long nk_min = GA_KNOB("TN2_PART_MIN", 65536);      // 256 x 256 outputs (CSWin proj) included: -0.2 ms/step there, neutral elsewhere
-    return (split > 1 && nk >= nk_min) ? (size_t)d->batch * split * nk * sizeof(float) : 0;   // small outputs: atomics are cheaper
+int lds_error(int bytes) {
+    ga_set_error("ga_gemm: cannot reserve %d bytes of LDS", bytes);
+    return GA_ERR_HIP;
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // persistent grid = exactly the number of workgroups that are resident at once (occupancy query per variant),
 // rounded down to a multiple of 8 so every XCD gets the same share of the tile walk
 template <typename T, int TNW, int NWM, bool PLAIN, bool PRE, int EPI, bool DMA = false>
-void launch_nt_(const ga_gemm_desc* d, hipStream_t s) {
+int launch_nt_(const ga_gemm_desc* d, hipStream_t s) {
     using CF = NTCfg<TNW, NWM>;
     constexpr int smem = DMA ? CF::SMEM_DMA : CF::SMEM;
     auto kern = gemm_nt_kernel<T, TNW, NWM, PLAIN, PRE, EPI, DMA>;
@@ -2054,26 +2032,21 @@ void launch_nt_(const ga_gemm_desc* d, hipStream_t s) {
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, CF::NTHR, smem) != hipSuccess || n < 1) n = 1;
         return n;
     }();
-    if (per_cu == 0) {
-        ga_set_error("ga_gemm: cannot reserve %d bytes of LDS", smem);
-        return;
-    }
+    if (per_cu == 0) return lds_error(smem);
     const int tiles = cdiv(d->M, CF::BM) * cdiv(d->N, CF::BN);
-    const int cap = std::max(8, (per_cu * num_cus() / d->batch) / 8 * 8);
+    const int cap = std::max(8, (per_cu * ga_num_cus() / d->batch) / 8 * 8);
     dim3 grid(std::min(tiles, cap), 1, d->batch), block(CF::NTHR);
     hipLaunchKernelGGL(kern, grid, block, smem, s, *d);
+    return ga_check_launch("ga_gemm");
 }
 
 template <int EPI>
-void launch_nt_pp(const ga_gemm_desc* d, hipStream_t s) {
+int launch_nt_pp(const ga_gemm_desc* d, hipStream_t s) {
     auto kern = gemm_nt_pp_kernel<EPI>;
     static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kPPSmem) == hipSuccess;
-    if (!ok) {
-        ga_set_error("ga_gemm: cannot reserve %d bytes of LDS", kPPSmem);
-        return;
-    }
+    if (!ok) return lds_error(kPPSmem);
     const int tiles = cdiv(d->M, 256) * cdiv(d->N, 256);
-    const int cap = std::max(8, (num_cus() / d->batch) / 8 * 8);
+    const int cap = std::max(8, (ga_num_cus() / d->batch) / 8 * 8);
     dim3 grid(std::min(tiles, cap), 1, d->batch), block(kPPThreads);
 #ifdef GAEXT_DEBUG
     const int dbg = GA_KNOB("PP_DBG", 0);         // timing experiments of the body (RESULTS DELIBERATELY WRONG): debug builds only
@@ -2081,27 +2054,26 @@ void launch_nt_pp(const ga_gemm_desc* d, hipStream_t s) {
     const int dbg = 0;
 #endif
     hipLaunchKernelGGL(kern, grid, block, kPPSmem, s, *d, dbg);
+    return ga_check_launch("ga_gemm");
 }
 
 template <int EPI, int DBG = 0, int AK = 0>
-void launch_nt_r3_(const ga_gemm_desc* d, hipStream_t s) {
+int launch_nt_r3_(const ga_gemm_desc* d, hipStream_t s) {
     auto kern = gemm_nt_r3_kernel<EPI, DBG, AK>;
     static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kR3Smem) == hipSuccess;
-    if (!ok) {
-        ga_set_error("ga_gemm: cannot reserve %d bytes of LDS", kR3Smem);
-        return;
-    }
+    if (!ok) return lds_error(kR3Smem);
     const int tiles = cdiv(d->M, 256) * cdiv(d->N, 128);
-    const int cap = std::max(8, (2 * num_cus() / d->batch) / 8 * 8);       // two workgroups per CU
+    const int cap = std::max(8, (2 * ga_num_cus() / d->batch) / 8 * 8);       // two workgroups per CU
     dim3 grid(std::min(tiles, cap), 1, d->batch), block(kR3Threads);
     // start skew of the second workgroup of a CU, in units of 64 clocks.  Off by default: measured 0, 40, 80, 160, 240 on the
     // MLP shapes of stages 1-3 (tools/r3_ab.py, R3_ARMS): within +-3 % of each other, no trend -- the two workgroups of a CU do
     // not run in lockstep, their phases add up because each is bound by the CU's shared issue / LDS paths
     const int stagger = std::max(0, GA_KNOB("R3_STAGGER", 0));
     hipLaunchKernelGGL(kern, grid, block, kR3Smem, s, *d, stagger);
+    return ga_check_launch("ga_gemm");
 }
 template <int EPI>
-void launch_nt_r3(const ga_gemm_desc* d, hipStream_t s) {
+int launch_nt_r3(const ga_gemm_desc* d, hipStream_t s) {
 #ifdef GAEXT_DEBUG
     switch (GA_KNOB("R3_DBG", 0)) {     // the timing-experiment variants exist in debug builds only
         case 1: return launch_nt_r3_<EPI, 1>(d, s);
@@ -2115,339 +2087,128 @@ void launch_nt_r3(const ga_gemm_desc* d, hipStream_t s) {
         default: break;
     }
 #endif
-    launch_nt_r3_<EPI, 0>(d, s);
+    return launch_nt_r3_<EPI, 0>(d, s);
 }
 
-// 3-slot ring form (256 x 128 tiles, two workgroups per CU): NT_R3 = bit mask of epilogues (1 plain, 2 fc1, 4 fc2, 8 dgrad2);
-// -1 = the heuristic below
-bool want_pp(const ga_gemm_desc* d, int epi);
-bool want_r3(const ga_gemm_desc* d, int epi) {
-    const int r3 = GA_KNOB("NT_R3", -1);
-    const bool forced = r3 >= 0;
-    const int mask = forced ? r3 : 15;
-    const bool neigh2 = d->a_kind == GA_A_NEIGH2;       // 2 x 2 neighbourhoods (data gradient of the 3 x 3 / stride-2 convs): plain epilogue only
-    const bool conv3s2 = d->a_kind == GA_A_CONV3S2;     // the 3 x 3 / stride-2 convs on even maps: plain epilogue only
-    const bool patch2 = d->a_kind == GA_A_PATCH2 || neigh2 || conv3s2;   // 2 x 2 / stride-2 patches (downsample convs): plain epilogue only
-    if (patch2 && (epi != EPI_PLAIN || d->a_C % 16 != 0 || d->K != (conv3s2 ? 9 : 4) * d->a_C || 4L * d->M * d->a_C >= (1L << 30) ||
-                   d->a_batch_mod || d->batch != 1))
-        return false;
-    if (neigh2 && (d->a_C % 32 != 0 || (long)d->M % ((long)d->a_H * d->a_W) != 0 || !GA_KNOB("NT_R3_NEIGH2", 1))) return false;
-    if (conv3s2 && (d->a_C % 32 != 0 || d->a_H % 2 != 0 || d->a_W % 2 != 0 || d->a_W < 4 ||
-                    (long)d->M % ((long)(d->a_H / 2) * (d->a_W / 2)) != 0 || !GA_KNOB("NT_R3_CONV3S2", 1)))
-        return false;
-    if (!mask || d->dtype != GA_BF16 || (d->a_kind != GA_A_PLAIN && !patch2) || epi == EPI_GENERIC || !((mask >> epi) & 1)) return false;
-    if (d->N % 8 != 0 || d->K % 8 != 0 || d->K < 64 || (!patch2 && d->lda % 8 != 0) || d->ldb % 8 != 0 || d->ldc % 8 != 0) return false;
-    if ((!patch2 && (long)d->M * d->lda >= (1L << 30)) || (long)d->N * d->ldb >= (1L << 30)) return false;   // 32-bit byte offsets
-    if ((reinterpret_cast<uintptr_t>(d->A) | reinterpret_cast<uintptr_t>(d->B) | reinterpret_cast<uintptr_t>(d->C)) & 15) return false;
-    const bool unpatch2 = d->c_kind == GA_C_UNPATCH2;   // scatter of the downsample conv's data gradient: plain epilogue only
-    if (unpatch2 && (epi != EPI_PLAIN || d->colsum || d->c_C % 8 != 0 || d->N != 4 * d->c_C || 4L * d->M * d->c_C >= (1L << 30) || d->batch != 1))
-        return false;
-    if ((!unpatch2 && (long)d->M * d->ldc >= (1L << 30)) || (d->c_kind != GA_C_PLAIN && !unpatch2) || d->c_f32) return false;
-    if (epi == EPI_FC1 && d->C2 && (reinterpret_cast<uintptr_t>(d->C2) & 15)) return false;
-    if (epi == EPI_DG2 && (d->ldh % 8 != 0 || (reinterpret_cast<uintptr_t>(d->H) & 15) || (long)d->M * d->ldh >= (1L << 30))) return false;
-    if (epi == EPI_FC2 && (d->ldr % 8 != 0 || (reinterpret_cast<uintptr_t>(d->R) & 15) || (long)d->M * d->ldr >= (1L << 30))) return false;
-    if (d->bias && (reinterpret_cast<uintptr_t>(d->bias) & 3)) return false;
-    if (forced) return true;
-    // heuristic from same-process A/B rounds against the other forms (tools/r3_ab.py, gpurun_out/r03/r3_ab*.log; MI355X):
-    //   fc1 / fc2 / dgrad2 epilogues at M = 6,272 .. 200,704, K = 192 .. 3072: x1.04 .. 1.76 everywhere measured
-    //   plain: ahead for K <= 512 (x1.13 .. 1.18) and for the K = 768 .. 2208 launches of the heads (x1.03 .. 1.10); behind the
-    //   8-wave ping-pong body on very wide / very long / very tall launches (N 2208: x0.91, K 3072: x0.83, 8192^3: x0.88,
-    //   M 73,856 of the ViT trunk: x0.91 .. 0.97) and behind the 128-column forms at N < 384 with a mid-length K (x0.95)
-    // gather kinds: the alternative is the register-staged gather (110-240 TFLOP/s on these launches, 0.105 ms for the 100 tiles
-    // of merge3's half-batch forward against 0.03 here)
-    if (neigh2 || conv3s2) return (long)cdiv(d->M, 256) * cdiv(d->N, 128) >= 16;
-    if ((long)cdiv(d->M, 256) * cdiv(d->N, 128) * d->batch < num_cus() / 2) return false;      // too few tiles to fill the chip
-    const bool pp = want_pp(d, epi);
-    if (d->M >= 65536 && pp) return false;
-    if (epi != EPI_PLAIN) return true;
-    if (d->K <= 512) return true;
-    if (pp) return d->N < 2048 && d->K < 3072;
-    return d->N >= 384 ? d->K < 3072 : d->K >= 1024;
-}
-
-// 8-wave ping-pong form: GAEXT_NT_PP = bit mask of epilogues (1 plain, 2 fc1, 4 fc2, 8 dgrad2); unset: plain / fc1 / fc2, for
-// launches whose K loop is long enough to carry the un-overlapped epilogue (K >= GAEXT_NT_PP_MINK, default 512) and whose
-// last column tile is not mostly empty
-bool want_pp(const ga_gemm_desc* d, int epi) {
-    const int pp = GA_KNOB("NT_PP", -1);    // -1: heuristic
-    const bool e = pp >= 0;
-    const int mask = e ? pp : 7;            // (dgrad2: its stored-GELU' operand is read inside the un-overlapped epilogue: measured slower)
-    const int mink = GA_KNOB("NT_PP_MINK", 512);
-    if (!mask || d->dtype != GA_BF16 || d->a_kind != GA_A_PLAIN || epi == EPI_GENERIC || !((mask >> epi) & 1)) return false;
-    if (d->N % 8 != 0 || d->K % 8 != 0 || d->K < (e ? 256 : mink) || d->lda % 8 != 0 || d->ldb % 8 != 0 || d->ldc % 8 != 0) return false;
-    if ((long)d->M * d->lda >= (1L << 30) || (long)d->N * d->ldb >= (1L << 30) || d->lda < 64 || d->ldb < 64) return false;   // 32-bit byte offsets
-    if ((reinterpret_cast<uintptr_t>(d->A) | reinterpret_cast<uintptr_t>(d->B) | reinterpret_cast<uintptr_t>(d->C)) & 15) return false;
-    if (epi == EPI_FC1 && d->C2 && (reinterpret_cast<uintptr_t>(d->C2) & 15)) return false;
-    if (epi == EPI_DG2 && (d->ldh % 8 != 0 || (reinterpret_cast<uintptr_t>(d->H) & 15))) return false;
-    if (epi == EPI_FC2 && (d->ldr % 8 != 0 || (reinterpret_cast<uintptr_t>(d->R) & 15))) return false;
-    const int tn = cdiv(d->N, 256);
-    if (!e && tn * 256 - d->N > tn * 256 / 8) return false;        // > 12.5 % of the column tiles' MFMA work on columns that do not exist
-    return (long)cdiv(d->M, 256) * tn * d->batch >= num_cus() / 2;
-}
-
-// pick the compile-time epilogue when the launch matches one of the hot shapes of the training step
-int classify_epilogue(const ga_gemm_desc* d, bool allow_patch2 = false) {
-    if ((d->a_kind != GA_A_PLAIN && !(allow_patch2 && (d->a_kind == GA_A_PATCH2 || d->a_kind == GA_A_NEIGH2 || d->a_kind == GA_A_CONV3S2))) ||
-        d->a_act != GA_ACT_NONE ||
-        d->alpha != 1.0f ||
-        (d->c_kind != GA_C_PLAIN && !(allow_patch2 && d->c_kind == GA_C_UNPATCH2)) || d->c_f32 ||
-        d->relu_after)
-        return EPI_GENERIC;
-    const bool act0 = d->act == GA_ACT_NONE;
-    if (d->act == GA_ACT_GELU && (!d->C2 || d->c2_mode == 2) && !d->H && !d->R && !d->rowscale && !d->colsum) return EPI_FC1;
-    if (act0 && !d->C2 && !d->H && d->R && !d->colsum) return EPI_FC2;
-    if (act0 && !d->C2 && d->H && d->h_is_deriv && !d->R && !d->rowscale) return EPI_DG2;
-    if (act0 && !d->C2 && !d->H && !d->R && !d->rowscale) return EPI_PLAIN;
-    return EPI_GENERIC;
-}
-
-// 256-row tiles (8 waves, one workgroup per CU) for the two epilogues that carry a prefetched epilogue operand
-// (fc2: + shortcut, dgrad2: * gelu'): their 4-wave form sits at 160-170 VGPRs = 2 workgroups per CU, and the wide
-// tile reads the weight slab once per 256 rows.  Measured on MI355X (tools/gemm_bench.py): dgrad2 1.35-1.45x,
-// fc2 1.1-1.2x; the plain / fc1 epilogues (120 VGPRs, 4 workgroups per CU) are 5-15 % SLOWER with it.
-bool want_big_tile(const ga_gemm_desc* d, int epi) {
-    const int force = GA_KNOB("NT_BIG", -1);      // 0 / 1 override for experiments; -1 = heuristic
-    if (d->dtype != GA_BF16 || d->a_kind != GA_A_PLAIN || (epi != EPI_FC2 && epi != EPI_DG2)) return false;
-    if (force >= 0) return force != 0;
-    return (long)cdiv(d->M, 256) * cdiv(d->N, 128) * d->batch >= 2L * num_cus();
-}
-
-// LDS-DMA form: 256-row tiles, plain bf16 operands, one of the compile-time epilogues
-// the LDS-DMA forms address their operands with 32-bit byte offsets from the matrix base
-bool dma_offsets_fit(const ga_gemm_desc* d) { return (long)d->M * d->lda < (1L << 30) && (long)d->N * d->ldb < (1L << 30); }
-
-bool want_dma(const ga_gemm_desc* d, int epi, int tnw) {
-    const int mode = GA_KNOB("NT_DMA", 1);        // 0 off, 1 heuristic (default), 2 every eligible launch
-    if (!mode || d->dtype != GA_BF16 || d->a_kind != GA_A_PLAIN || epi == EPI_GENERIC || (tnw != 4 && tnw != 3) || !dma_offsets_fit(d)) return false;
-    if ((long)cdiv(d->M, 256) * cdiv(d->N, 32 * tnw) * d->batch < num_cus()) return false;
-    // measured (tools/gemm_bench.py): ahead only for the fc2 epilogue with a long reduction (K >= 1024, +8..20 %);
-    // mode 2 forces it on every eligible launch (tests, experiments)
-    return mode == 2 || (epi == EPI_FC2 && tnw == 4 && d->K >= 1024);
-}
-
-// 128 x 128 tile, 4 waves, LDS-DMA into a 2-slot ring, 80 KiB: two workgroups per CU without the ds_write staging pass
-bool want_dma2(const ga_gemm_desc* d, int epi) {
-    // NT_DMA2: bit mask of epilogues (1 plain, 2 fc1, 4 fc2, 8 dgrad2)
-    // unset: fc1 and dgrad2 (stage-2 shapes, same box, after the DMA went through buffer resources: fc1 0.126 -> 0.119 ms,
-    // dgrad2 0.137 -> 0.118; fc2 / dgrad1 are 3-5 % slower with it and keep the register-staged form)
-    const int mask = GA_KNOB("NT_DMA2", 10);
-    if (!mask || d->dtype != GA_BF16 || d->a_kind != GA_A_PLAIN || epi == EPI_GENERIC || !dma_offsets_fit(d)) return false;
-    if (d->K < GA_KNOB("NT_DMA2_MINK", 256)) return false;
-    return (mask >> epi) & 1;
-}
-
-// 256 x 256 tile, 8 waves (64 x 128 each), LDS-DMA into a 2-slot ring: wide-N launches
-bool want_t256(const ga_gemm_desc* d, int epi) {
-    const int t256 = GA_KNOB("NT_T256", -1);      // bit mask of epilogues (1 plain, 2 fc1, 4 fc2, 8 dgrad2); -1: heuristic
-    // unset: every epilogue, but only for the very tall launches (M >= 65536: the ViT trunk's 73,856 token rows, -4.8 % on the
-    // MAP-ViT-B/384 step); on the ConvNeXt / CSWin stage-2/3 shapes (M = 50,176) the form measured -12 .. +5 % and stays off
-    const int mask = t256 >= 0 ? t256 : ((d->M >= 65536 && d->N >= 768) ? 15 : 0);      // (N >= 768: the CSWin stem's N = 256 launches lose 2 %)
-    if (!mask || d->dtype != GA_BF16 || d->a_kind != GA_A_PLAIN || epi == EPI_GENERIC || !dma_offsets_fit(d)) return false;
-    if (d->N % 256 != 0 || d->K < 256) return false;
-    if ((long)cdiv(d->M, 256) * (d->N / 256) * d->batch < num_cus()) return false;
-    return (mask >> epi) & 1;
-}
-
-template <typename T, int TNW, int NWM>
-void launch_nt(const ga_gemm_desc* d, hipStream_t s) {
-    constexpr bool BF = sizeof(T) == 2;   // the epilogue-operand prefetch exists for bf16 only (32 extra VGPRs)
-    if (d->a_kind != GA_A_PLAIN) {
-        launch_nt_<T, TNW, NWM, false, false, EPI_GENERIC>(d, s);
-        return;
+// run-time epilogue -> compile-time instantiation: f(std::integral_constant<int, EPI>).  GENERIC: the form has a generic
+// epilogue (the register-staged tiles only; the selection names no other form with it)
+template <bool GENERIC, typename F>
+int with_epi(int epi, F&& f) {
+    switch (epi) {
+        case EPI_PLAIN: return f(std::integral_constant<int, EPI_PLAIN>{});
+        case EPI_FC1: return f(std::integral_constant<int, EPI_FC1>{});
+        case EPI_FC2: return f(std::integral_constant<int, EPI_FC2>{});
+        case EPI_DG2: return f(std::integral_constant<int, EPI_DG2>{});
+        default: break;
     }
-    switch (classify_epilogue(d)) {
-        case EPI_PLAIN: launch_nt_<T, TNW, NWM, true, false, EPI_PLAIN>(d, s); break;
-        case EPI_FC1: launch_nt_<T, TNW, NWM, true, false, EPI_FC1>(d, s); break;
-        case EPI_FC2: launch_nt_<T, TNW, NWM, true, BF, EPI_FC2>(d, s); break;
-        case EPI_DG2: launch_nt_<T, TNW, NWM, true, BF, EPI_DG2>(d, s); break;
+    if constexpr (GENERIC) return f(std::integral_constant<int, EPI_GENERIC>{});
+    ga_set_error("ga_gemm: form without a generic epilogue");
+    return GA_ERR_BAD_ARG;
+}
+
+// the gemm_nt_kernel tiles: operand type, tile and LDS-DMA come with the form, epilogue and prefetch with the selection
+template <typename T, int TNW, int NWM, bool DMA>
+int launch_nt_tile(const ga_gemm_desc* d, const NtSel& sel, hipStream_t s) {
+    return with_epi<!DMA>(sel.epi, [&](auto e) {
+        constexpr int EPI = decltype(e)::value;
+        // the epilogue-operand prefetch exists for bf16 only (32 extra VGPRs), and not in the 256-column tile
+        constexpr bool PRE = sizeof(T) == 2 && TNW != 8 && EPI != EPI_PLAIN && EPI != EPI_FC1;
+        if constexpr (EPI == EPI_GENERIC) {
+            if (d->a_kind != GA_A_PLAIN) return launch_nt_<T, TNW, NWM, false, false, EPI_GENERIC>(d, s);
+            if (!sel.pre) return launch_nt_<T, TNW, NWM, true, false, EPI_GENERIC>(d, s);
+        }
+        return launch_nt_<T, TNW, NWM, true, PRE, EPI, DMA>(d, s);
+    });
+}
+template <typename T>
+int launch_nt_staged(const ga_gemm_desc* d, const NtSel& sel, hipStream_t s) {
+    if (sel.tnw == 4) return launch_nt_tile<T, 4, 2, false>(d, sel, s);
+    if (sel.tnw == 3) return launch_nt_tile<T, 3, 2, false>(d, sel, s);
+    return launch_nt_tile<T, 2, 2, false>(d, sel, s);
+}
+
+int launch_nt_form(const ga_gemm_desc* d, const NtSel& sel, hipStream_t s) {
+    switch (sel.form) {
+        case NT_R3G: return launch_nt_r3_<EPI_PLAIN, 0, 1>(d, s);
+        case NT_R3: return with_epi<false>(sel.epi, [&](auto e) { return launch_nt_r3<decltype(e)::value>(d, s); });
+        case NT_DMA256:
+            return sel.tnw == 4 ? launch_nt_tile<bf16_t, 4, 4, true>(d, sel, s) : launch_nt_tile<bf16_t, 3, 4, true>(d, sel, s);
+        case NT_PP: return with_epi<false>(sel.epi, [&](auto e) { return launch_nt_pp<decltype(e)::value>(d, s); });
+        case NT_T256: return launch_nt_tile<bf16_t, 8, 4, true>(d, sel, s);
+        case NT_DMA128: return launch_nt_tile<bf16_t, 4, 2, true>(d, sel, s);
+        case NT_BIG:
+            return sel.epi == EPI_FC2 ? launch_nt_<bf16_t, 4, 4, true, true, EPI_FC2>(d, s)
+                                      : launch_nt_<bf16_t, 4, 4, true, true, EPI_DG2>(d, s);
         default:
-            if (BF && (d->H || d->R)) launch_nt_<T, TNW, NWM, true, BF, EPI_GENERIC>(d, s);
-            else launch_nt_<T, TNW, NWM, true, false, EPI_GENERIC>(d, s);
+            return d->dtype == GA_BF16 ? launch_nt_staged<bf16_t>(d, sel, s) : launch_nt_staged<float>(d, sel, s);
+    }
+}
+
+int launch_tn2(const ga_wgrad_desc* d, const TnSel& sel, hipStream_t s) {
+    static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn2_kernel<false>),
+                                                    hipFuncAttributeMaxDynamicSharedMemorySize, kTn2Smem) == hipSuccess &&
+                                hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn2_kernel<true>),
+                                                    hipFuncAttributeMaxDynamicSharedMemorySize, kTn2Smem) == hipSuccess;
+    GA_REQUIRE(attr_ok, "ga_wgrad: cannot reserve %d bytes of LDS", kTn2Smem);
+    const int split = sel.split;
+    dim3 grid2(cdiv(d->N, 256) * cdiv(d->K, 256) * split, 1, d->batch), block2(kTn2Threads);
+    float* part = sel.partials ? reinterpret_cast<float*>(d->workspace) : nullptr;
+    GA_REQUIRE(!part || aligned16(part), "ga_wgrad: workspace must be 16-byte aligned");
+    const long nk = (long)d->N * d->K;
+    if (d->x_kind == GA_A_PATCH2) hipLaunchKernelGGL(gemm_tn2_kernel<true>, grid2, block2, kTn2Smem, s, *d, split, part);
+    else hipLaunchKernelGGL(gemm_tn2_kernel<false>, grid2, block2, kTn2Smem, s, *d, split, part);
+    if (part)
+        hipLaunchKernelGGL(tn2_reduce_kernel, dim3((unsigned)std::min<long>(2048, cdiv(nk, 1024)), d->batch), dim3(256),
+                           0, s, part, split, nk, d->K, d->alpha, d->dW, d->ldw, d->strideW);
+    return ga_check_launch("ga_wgrad");
+}
+
+// the direct kernels of conv3.hip: 0 when the kernel's LDS cannot be reserved (nothing was launched)
+int launch_tn_direct(const ga_wgrad_desc* d, const TnSel& sel, hipStream_t s) {
+    switch (sel.form) {
+        case TN_CONV3_DIRECT: return ga_conv3_c64_wgrad_launch(d, sel.split, s);        // 64 -> 64 channels
+        case TN_CONV3S2_DIRECT: return ga_conv3s2_c64_wgrad_launch(d, sel.split, s);    // ... stride 2
+        case TN_CONV0_DIRECT: return ga_conv0_c8_wgrad_launch(d, sel.split, s);         // 3 (8) -> 64, stride 2
+        default: return ga_stem4_wgrad_launch(d, sel.split, s);                         // ConvNeXt stem
     }
 }
 
 }  // namespace
 
 extern "C" int ga_gemm(const ga_gemm_desc* d, ga_stream_t stream) {
-    GA_REQUIRE(d && d->A && d->B && d->C, "ga_gemm: null operand");
-    GA_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0 && d->batch >= 1, "ga_gemm: bad shape M=%d N=%d K=%d batch=%d", d->M,
-               d->N, d->K, d->batch);
-    GA_REQUIRE(d->dtype == GA_F32 || d->dtype == GA_BF16, "ga_gemm: bad dtype %d", d->dtype);
-    const int epc = d->dtype == GA_BF16 ? 8 : 4;
-    GA_REQUIRE(aligned16(d->A) && aligned16(d->B) && aligned16(d->C), "ga_gemm: operands must be 16-byte aligned");
-    GA_REQUIRE(d->ldb % epc == 0 && d->strideB % epc == 0, "ga_gemm: ldb/strideB must be multiples of %d", epc);
-    GA_REQUIRE(d->K % epc == 0, "ga_gemm: K=%d must be a multiple of %d (pad the operand)", d->K, epc);
-    if (d->a_kind == GA_A_PLAIN) {
-        GA_REQUIRE(d->lda % epc == 0 && d->strideA % epc == 0, "ga_gemm: lda/strideA must be multiples of %d", epc);
-    } else if (d->a_kind == GA_A_PATCH2) {
-        GA_REQUIRE(d->a_C % epc == 0 && d->a_H % 2 == 0 && d->a_W % 2 == 0 && d->K == 4 * d->a_C &&
-                       (long)d->M % ((d->a_H / 2) * (d->a_W / 2)) == 0,
-                   "ga_gemm: PATCH2 needs C%%%d==0, even H,W, K==4C", epc);
-    } else if (d->a_kind == GA_A_CONV3) {
-        GA_REQUIRE(d->a_C % epc == 0 && d->K == 9 * d->a_C && (long)d->M % (d->a_H * d->a_W) == 0,
-                   "ga_gemm: CONV3 needs C%%%d==0, K==9C", epc);
-    } else if (d->a_kind == GA_A_CONV3S2) {
-        GA_REQUIRE(d->a_C % epc == 0 && d->K == 9 * d->a_C && (long)d->M % (((d->a_H + 1) / 2) * ((d->a_W + 1) / 2)) == 0,
-                   "ga_gemm: CONV3S2 needs C%%%d==0, K==9C", epc);
-    } else if (d->a_kind == GA_A_NEIGH2) {
-        GA_REQUIRE(d->a_C % epc == 0 && d->K == 4 * d->a_C && (long)d->M % (d->a_H * d->a_W) == 0,
-                   "ga_gemm: NEIGH2 needs C%%%d==0, K==4C", epc);
-    } else if (d->a_kind == GA_A_STEM4_NCHW) {
-        GA_REQUIRE(d->a_C == 3 && d->K == 48 && d->a_H % 4 == 0 && d->a_W % 4 == 0, "ga_gemm: STEM4 needs C=3,K=48");
-    } else {
-        GA_REQUIRE(false, "ga_gemm: bad a_kind %d", d->a_kind);
-    }
-    if (d->c_kind == GA_C_UNPATCH2) {
-        GA_REQUIRE(d->c_C % 8 == 0 && d->N == 4 * d->c_C && !d->c_f32, "ga_gemm: UNPATCH2 needs N==4*c_C, c_C%%8==0");
-    } else {
-        GA_REQUIRE(d->c_kind == GA_C_PLAIN, "ga_gemm: bad c_kind");
-    }
-    if (d->H) GA_REQUIRE(aligned16(d->H) && d->ldh % 8 == 0, "ga_gemm: H alignment");
-    if (d->C2) GA_REQUIRE(aligned16(d->C2) && d->c_kind == GA_C_PLAIN && !d->c_f32 && (d->c2_mode == 1 || d->c2_mode == 2),
-                          "ga_gemm: C2 needs a plain, dtype-typed C and c2_mode 1|2");
-    if (d->R) GA_REQUIRE(aligned16(d->R) && d->ldr % 8 == 0, "ga_gemm: R alignment");
-    if (d->rowscale) GA_REQUIRE(d->rows_per_scale > 0, "ga_gemm: rows_per_scale");
-    // vector stores need an 8-element aligned leading dimension; otherwise every piece takes the scalar path,
-    // which the kernel selects per piece only at the N edge -> require it here.
-    GA_REQUIRE(d->c_kind != GA_C_PLAIN || d->ldc % 8 == 0, "ga_gemm: ldc=%ld must be a multiple of 8", (long)d->ldc);
-    // N-tile width: 128 when it divides N, else 96 (stage-0 C = 96, concat 2208 = 23*96), else 64; ragged N -> least waste
-    int tnw;
-    if (d->N % 128 == 0) tnw = 4;
-    else if (d->N % 96 == 0) tnw = 3;
-    else if (d->N % 64 == 0) tnw = 2;
-    else {
-        const long w4 = (long)cdiv(d->N, 128) * 128, w3 = (long)cdiv(d->N, 96) * 96, w2 = (long)cdiv(d->N, 64) * 64;
-        tnw = (w4 <= w3 && w4 <= w2) ? 4 : (w3 <= w2 ? 3 : 2);
-    }
+    if (const int rc = nt_validate(d)) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool bf = d->dtype == GA_BF16;
-#define GA_LAUNCH_NT(TNW, NWM)                          \
-    do {                                               \
-        if (bf) launch_nt<bf16_t, TNW, NWM>(d, s);     \
-        else launch_nt<float, TNW, NWM>(d, s);         \
-    } while (0)
-    if (d->a_kind == GA_A_CONV3 && ga_conv3_c64_try(d, s)) return ga_check_launch("ga_gemm");     // 64 -> 64 channels: direct convolution
-    if (d->a_kind == GA_A_CONV3S2 && d->a_C == 8 && ga_conv0_c8_try(d, s)) return ga_check_launch("ga_gemm");   // 3 (8) -> 64: first conv of the deep stem
-    const int epi = classify_epilogue(d);
-    if ((d->a_kind == GA_A_PATCH2 || d->a_kind == GA_A_NEIGH2 || d->a_kind == GA_A_CONV3S2 || d->c_kind == GA_C_UNPATCH2) &&
-        classify_epilogue(d, true) == EPI_PLAIN &&
-        want_r3(d, EPI_PLAIN)) {
-        if (d->a_kind == GA_A_NEIGH2 || d->a_kind == GA_A_CONV3S2) launch_nt_r3_<EPI_PLAIN, 0, 1>(d, s);
-        else launch_nt_r3<EPI_PLAIN>(d, s);          // downsample conv (2 x 2 / stride 2) straight from the NHWC map / its data gradient
+    Knobs k = current_knobs();
+    NtSel sel = nt_select(d, ga_num_cus(), k);
+    if (sel.form == NT_CONV3_DIRECT) {            // 64 -> 64 channels: direct convolution
+        if (ga_conv3_c64_launch(d, s)) return ga_check_launch("ga_gemm");
+        k.CONV3_DIRECT = 0;                       // its LDS cannot be reserved: the gather GEMM takes the launch
+        sel = nt_select(d, ga_num_cus(), k);
+    }
+    if (sel.form == NT_CONV0_DIRECT) {            // 3 (8) -> 64: first conv of the deep stem
+        ga_conv0_c8_launch(d, s);
         return ga_check_launch("ga_gemm");
     }
-    if (want_r3(d, epi)) {
-        switch (epi) {
-            case EPI_PLAIN: launch_nt_r3<EPI_PLAIN>(d, s); break;
-            case EPI_FC1: launch_nt_r3<EPI_FC1>(d, s); break;
-            case EPI_FC2: launch_nt_r3<EPI_FC2>(d, s); break;
-            default: launch_nt_r3<EPI_DG2>(d, s); break;
-        }
-    } else if (want_dma(d, epi, tnw)) {
-        if (tnw == 4) {
-            switch (epi) {
-                case EPI_PLAIN: launch_nt_<bf16_t, 4, 4, true, false, EPI_PLAIN, true>(d, s); break;
-                case EPI_FC1: launch_nt_<bf16_t, 4, 4, true, false, EPI_FC1, true>(d, s); break;
-                case EPI_FC2: launch_nt_<bf16_t, 4, 4, true, true, EPI_FC2, true>(d, s); break;
-                default: launch_nt_<bf16_t, 4, 4, true, true, EPI_DG2, true>(d, s); break;
-            }
-        } else {
-            switch (epi) {
-                case EPI_PLAIN: launch_nt_<bf16_t, 3, 4, true, false, EPI_PLAIN, true>(d, s); break;
-                case EPI_FC1: launch_nt_<bf16_t, 3, 4, true, false, EPI_FC1, true>(d, s); break;
-                case EPI_FC2: launch_nt_<bf16_t, 3, 4, true, true, EPI_FC2, true>(d, s); break;
-                default: launch_nt_<bf16_t, 3, 4, true, true, EPI_DG2, true>(d, s); break;
-            }
-        }
-    } else if (want_pp(d, epi)) {
-        switch (epi) {
-            case EPI_PLAIN: launch_nt_pp<EPI_PLAIN>(d, s); break;
-            case EPI_FC1: launch_nt_pp<EPI_FC1>(d, s); break;
-            case EPI_FC2: launch_nt_pp<EPI_FC2>(d, s); break;
-            default: launch_nt_pp<EPI_DG2>(d, s); break;
-        }
-    } else if (want_t256(d, epi)) {
-        switch (epi) {
-            case EPI_PLAIN: launch_nt_<bf16_t, 8, 4, true, false, EPI_PLAIN, true>(d, s); break;
-            case EPI_FC1: launch_nt_<bf16_t, 8, 4, true, false, EPI_FC1, true>(d, s); break;
-            case EPI_FC2: launch_nt_<bf16_t, 8, 4, true, false, EPI_FC2, true>(d, s); break;
-            default: launch_nt_<bf16_t, 8, 4, true, false, EPI_DG2, true>(d, s); break;
-        }
-    } else if (tnw == 4 && want_dma2(d, epi)) {
-        switch (epi) {
-            case EPI_PLAIN: launch_nt_<bf16_t, 4, 2, true, false, EPI_PLAIN, true>(d, s); break;
-            case EPI_FC1: launch_nt_<bf16_t, 4, 2, true, false, EPI_FC1, true>(d, s); break;
-            case EPI_FC2: launch_nt_<bf16_t, 4, 2, true, true, EPI_FC2, true>(d, s); break;
-            default: launch_nt_<bf16_t, 4, 2, true, true, EPI_DG2, true>(d, s); break;
-        }
-    } else if (tnw == 4) {
-        if (want_big_tile(d, epi)) {
-            if (epi == EPI_FC2) launch_nt_<bf16_t, 4, 4, true, true, EPI_FC2>(d, s);
-            else launch_nt_<bf16_t, 4, 4, true, true, EPI_DG2>(d, s);
-        } else {
-            GA_LAUNCH_NT(4, 2);
-        }
-    } else if (tnw == 3) {
-        GA_LAUNCH_NT(3, 2);
-    } else {
-        GA_LAUNCH_NT(2, 2);
-    }
-#undef GA_LAUNCH_NT
-    return ga_check_launch("ga_gemm");
+    return launch_nt_form(d, sel, s);
+}
+
+extern "C" int ga_gemm_form(const ga_gemm_desc* d, char* buf, size_t n) {
+    if (const int rc = nt_validate(d)) return rc;
+    if (buf && n) nt_form_name(d, nt_select(d, ga_num_cus(), current_knobs()), buf, n);
+    return GA_OK;
 }
 
 extern "C" int ga_wgrad(const ga_wgrad_desc* d, ga_stream_t stream) {
-    GA_REQUIRE(d && d->Y && d->X && d->dW, "ga_wgrad: null operand");
-    GA_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0 && d->batch >= 1 && d->split_m >= 1, "ga_wgrad: bad shape");
-    GA_REQUIRE(d->dtype == GA_F32 || d->dtype == GA_BF16, "ga_wgrad: bad dtype %d", d->dtype);
-    const int epc = d->dtype == GA_BF16 ? 8 : 4;
-    GA_REQUIRE(aligned16(d->Y) && aligned16(d->X), "ga_wgrad: operands must be 16-byte aligned");
-    GA_REQUIRE(d->N % epc == 0 && d->ldy % epc == 0 && d->strideY % epc == 0, "ga_wgrad: N/ldy must be multiples of %d",
-               epc);
-    if (d->x_kind == GA_A_PLAIN) {
-        // K (an OUTPUT dim here) may be ragged as long as the X rows are padded to a chunk multiple
-        GA_REQUIRE(d->ldx % epc == 0 && d->strideX % epc == 0 && d->ldx >= (d->K + epc - 1) / epc * epc,
-                   "ga_wgrad: ldx must be a multiple of %d and cover K rounded up", epc);
-    } else if (d->x_kind == GA_A_PATCH2) {
-        GA_REQUIRE(d->x_C % epc == 0 && d->K == 4 * d->x_C, "ga_wgrad: PATCH2 needs K==4C");
-    } else if (d->x_kind == GA_A_CONV3) {
-        GA_REQUIRE(d->x_C % epc == 0 && d->K == 9 * d->x_C, "ga_wgrad: CONV3 needs K==9C");
-    } else if (d->x_kind == GA_A_CONV3S2) {
-        GA_REQUIRE(d->x_C % epc == 0 && d->K == 9 * d->x_C, "ga_wgrad: CONV3S2 needs K==9C");
-    } else if (d->x_kind == GA_A_NEIGH2) {
-        GA_REQUIRE(d->x_C % epc == 0 && d->K == 4 * d->x_C, "ga_wgrad: NEIGH2 needs K==4C");
-    } else if (d->x_kind == GA_A_STEM4_NCHW) {
-        GA_REQUIRE(d->x_C == 3 && d->K == 48, "ga_wgrad: STEM4 needs C=3,K=48");
-    } else {
-        GA_REQUIRE(false, "ga_wgrad: bad x_kind %d", d->x_kind);
-    }
+    if (const int rc = tn_validate(d)) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (d->x_kind == GA_A_CONV3 && ga_conv3_c64_wgrad_try(d, s)) return ga_check_launch("ga_wgrad");   // 64 -> 64 channels: direct form
-    if (d->x_kind == GA_A_CONV3S2 && d->x_C == 64 && ga_conv3s2_c64_wgrad_try(d, s)) return ga_check_launch("ga_wgrad");   // ... stride 2
-    if (d->x_kind == GA_A_CONV3S2 && d->x_C == 8 && ga_conv0_c8_wgrad_try(d, s)) return ga_check_launch("ga_wgrad");        // 3 (8) -> 64, stride 2
-    if (d->x_kind == GA_A_STEM4_NCHW && ga_stem4_wgrad_try(d, s)) return ga_check_launch("ga_wgrad");                       // ConvNeXt stem
-    if (tn2_eligible(d)) {
-        const bool p2 = d->x_kind == GA_A_PATCH2;
-        static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn2_kernel<false>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, kTn2Smem) == hipSuccess &&
-                                    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn2_kernel<true>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, kTn2Smem) == hipSuccess;
-        GA_REQUIRE(attr_ok, "ga_wgrad: cannot reserve %d bytes of LDS", kTn2Smem);
-        int split;
-        const size_t need = tn2_plan(d, &split);
-        dim3 grid2(cdiv(d->N, 256) * cdiv(d->K, 256) * split, 1, d->batch), block2(kTn2Threads);
-        // partial tiles + one reduce launch when the caller provided the workspace ga_wgrad_workspace() asks for; fp32 atomics
-        // into dW otherwise (slower for wide outputs, same result up to summation order)
-        float* part = (need && d->workspace && (size_t)d->ws_bytes >= need) ? reinterpret_cast<float*>(d->workspace) : nullptr;
-        GA_REQUIRE(!part || aligned16(part), "ga_wgrad: workspace must be 16-byte aligned");
-        const long nk = (long)d->N * d->K;
-        if (p2) hipLaunchKernelGGL(gemm_tn2_kernel<true>, grid2, block2, kTn2Smem, s, *d, split, part);
-        else hipLaunchKernelGGL(gemm_tn2_kernel<false>, grid2, block2, kTn2Smem, s, *d, split, part);
-        if (part)
-            hipLaunchKernelGGL(tn2_reduce_kernel, dim3((unsigned)std::min<long>(2048, cdiv(nk, 1024)), d->batch), dim3(256),
-                               0, s, part, split, nk, d->K, d->alpha, d->dW, d->ldw, d->strideW);
-        return ga_check_launch("ga_wgrad");
+    Knobs k = current_knobs();
+    TnSel sel = tn_select(d, ga_num_cus(), k);
+    if (sel.form <= TN_STEM4_DIRECT) {
+        if (launch_tn_direct(d, sel, s)) return ga_check_launch("ga_wgrad");
+        k.CONV3_DIRECT = k.CONV0_DIRECT = k.STEM4_WGRAD_DIRECT = 0;       // as in ga_gemm
+        sel = tn_select(d, ga_num_cus(), k);
     }
+    if (sel.form == TN_TN2) return launch_tn2(d, sel, s);
     dim3 grid(cdiv(d->N, 128) * cdiv(d->K, 128) * d->split_m, 1, d->batch), block(kThreads);
     if (d->dtype == GA_BF16)
         hipLaunchKernelGGL(gemm_tn_kernel<bf16_t>, grid, block, 65536, s, *d);
@@ -2456,11 +2217,13 @@ extern "C" int ga_wgrad(const ga_wgrad_desc* d, ga_stream_t stream) {
     return ga_check_launch("ga_wgrad");
 }
 
+extern "C" int ga_wgrad_form(const ga_wgrad_desc* d, char* buf, size_t n) {
+    if (const int rc = tn_validate(d)) return rc;
+    if (buf && n) tn_form_name(d, tn_select(d, ga_num_cus(), current_knobs()), buf, n);
+    return GA_OK;
+}
+
 extern "C" size_t ga_wgrad_workspace(const ga_wgrad_desc* d) {
     if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch < 1) return 0;
-    if (d->x_kind == GA_A_CONV3 || (d->x_kind == GA_A_CONV3S2 && (d->x_C == 64 || d->x_C == 8))) return ga_conv3_c64_wgrad_workspace(d);
-    if (d->x_kind == GA_A_STEM4_NCHW) return ga_stem4_wgrad_workspace(d);
-    if (!tn2_eligible(d)) return 0;
-    int split;
-    return tn2_plan(d, &split);
+    return tn_select(d, ga_num_cus(), current_knobs()).ws_bytes;
 }

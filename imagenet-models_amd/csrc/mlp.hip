@@ -642,15 +642,6 @@ extern "C" int ga_mlp_bwd_wgrad_supported(int C, int H, int dtype) { return dtyp
 
 namespace {
 
-int num_cus() {
-    static int n = [] {
-        int c = 256;
-        ga_device_info(&c, nullptr, nullptr);
-        return c;
-    }();
-    return n;
-}
-
 // persistent grid of the weight-gradient form: the workgroups that are resident at once (occupancy query, as the ring GEMM
 // does it), at most max_blocks when that is given, and never more than there are tiles -- so no workgroup is without a tile
 // and every partial is written.  0: the LDS cannot be reserved.
@@ -661,7 +652,7 @@ int wg_grid(const ga_mlp_bwd_desc* d) {
         if (!set_lds(kern, lds)) return 0;
         int n = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, 512, lds) != hipSuccess || n < 1) n = 1;
-        return n * num_cus();
+        return n * ga_num_cus();
     }();
     long grid = resident;
     if (d->max_blocks > 0) grid = std::min<long>(grid, d->max_blocks);

@@ -162,6 +162,15 @@ extern "C" int ga_device_info(int* num_cu, int* lds_bytes, int* wave_size) {
     return GA_OK;
 }
 
+int ga_num_cus() {
+    static const int n = [] {
+        int c = 256;      // no device (a host-only query of the kernel selection): the MI355X's count
+        ga_device_info(&c, nullptr, nullptr);
+        return c;
+    }();
+    return n;
+}
+
 extern "C" int ga_memset(void* p, int value, size_t bytes, ga_stream_t stream) {
     if (!p || !bytes) {
         ga_set_error("ga_memset: null/empty");

@@ -992,6 +992,21 @@ def mlp_bwd_partials(M, Cdim, dtype, max_blocks=0):
     return int(L.load().ga_mlp_bwd_partials(C.byref(d)))
 
 
+def gemm_form(d):
+    """name of the kernel form ga_gemm launches for this GemmDesc under the current knobs (include/gaext.h: ga_gemm_form);
+    raises as the launch would for a descriptor it rejects.  Needs no GPU."""
+    buf = C.create_string_buffer(64)
+    L.check(L.load().ga_gemm_form(C.byref(d), buf, 64), 'ga_gemm_form')
+    return buf.value.decode()
+
+
+def wgrad_form(d):
+    """... and ga_wgrad for this WgradDesc (ga_wgrad_form)"""
+    buf = C.create_string_buffer(64)
+    L.check(L.load().ga_wgrad_form(C.byref(d), buf, 64), 'ga_wgrad_form')
+    return buf.value.decode()
+
+
 def cswin_attn_bwd_workspace(d):
     """bytes of the LePE partial buffer Plan.cswin_attn_bwd takes for this descriptor (0: generic form, no fused partials)"""
     return int(L.load().ga_cswin_attn_bwd_workspace(C.byref(d)))

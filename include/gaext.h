@@ -151,6 +151,28 @@ int ga_wgrad(const ga_wgrad_desc* d, ga_stream_t stream);
  * workspaces; calls on one stream may share one. */
 size_t ga_wgrad_workspace(const ga_wgrad_desc* d);
 
+/* Which kernel form ga_gemm / ga_wgrad launches for a descriptor under the current knob table.  Validates exactly as the launch
+ * does (same return code, same ga_last_error message) and, on GA_OK, writes the form's stable name into buf (NUL-terminated,
+ * truncated to n).  Touches no device memory and launches nothing: it also works on a machine without a GPU, where the number
+ * of compute units is taken as 256.  The forms in the order they are tried, ":epilogue" = plain | fc1 | fc2 | dg2 | generic:
+ *   ga_gemm:  conv3_direct, conv0_direct          direct convolutions (64 -> 64 channels 3x3; 3 (8) -> 64 stride 2)
+ *             r3g:plain                           3-slot ring, 3x3/s2 and 2x2-neighbourhood gathers
+ *             r3:<epi>                            3-slot ring, 256 x 128 tiles (also GA_A_PATCH2 / GA_C_UNPATCH2 as r3:plain)
+ *             dma256x128:<epi> dma256x96:<epi>    256-row LDS-DMA tiles
+ *             pp:<epi>                            8-wave ping-pong, 256 x 256
+ *             t256:<epi>                          256 x 256 LDS-DMA
+ *             dma128:<epi>                        128 x 128 LDS-DMA
+ *             big:<epi>                           256 x 128 register-staged (fc2, dg2)
+ *             staged128|96|64:<epi>[+pre][+gather][+f32]   register-staged 128-row tiles: +pre prefetches the epilogue operand,
+ *                                                 +gather reads a gathered A, +f32 is the fp32 instantiation
+ *   ga_wgrad: conv3_wgrad_direct:wgs<G>, conv3s2_wgrad_direct:.., conv0_wgrad_direct:.., stem4_wgrad_direct:..   G workgroups with
+ *                                                 64*576 (conv0: 64*72, stem4: N*49) floats of workspace each; need d->workspace
+ *             tn2:split<S>:partials|atomics       wide 256 x 256 form with S row splits (partials: batch*S*N*K floats of
+ *                                                 workspace); tn2p: on a GA_A_PATCH2 operand
+ *             tn                                  128 x 128 form, split_m row splits */
+int ga_gemm_form(const ga_gemm_desc* d, char* buf, size_t n);
+int ga_wgrad_form(const ga_wgrad_desc* d, char* buf, size_t n);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Weight preparation: fp32 master conv/linear weight [G*Co][Ci][KH][KW]  ->  "effective" copies in `dtype`
  *   out [G][Co][ldo]  with k = (ky,kx,ci)   : out = rs[n] * w * cs[ci]          (B operand of the forward GEMM)

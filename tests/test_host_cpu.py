@@ -345,3 +345,146 @@ def test_asm_store_audit_flags_a_write_behind_a_16_byte_buffer_store(tmp_path):
         f.write_text(text)
         r = subprocess.run([sys.executable, tool, '--stores', str(f), 'my_kernel'], capture_output=True, text=True)
         assert r.returncode == rc, (text, r.stdout, r.stderr)
+
+
+def _gemm_forms_tool():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('gemm_forms', os.path.join(ROOT, 'tools', 'gemm_forms.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    mod.prime()
+    return mod
+
+
+def test_kernel_form_selection_matches_the_recorded_corpus():
+    """ga_gemm_form / ga_wgrad_form (and ga_wgrad_workspace) over tests/golden/gemm_forms.json -- the descriptors of the forced-form GPU
+    tests under their knobs and of the model engines at the bench batch -- name the recorded forms; the test part of the corpus is the
+    one tools/gemm_forms.py restates from the tests"""
+    import json
+    T = _gemm_forms_tool()
+    recorded = json.load(open(T.GOLDEN))
+    assert len(recorded) > 400 and any(not c['src'].startswith('test_') for c in recorded)
+    bad = [(c['src'], c.get('knobs'), c['desc'], T.answer(c), c['form']) for c in recorded if T.answer(c) != c['form']]
+    assert not bad, bad[:5]
+    strip = lambda c: {k: c[k] for k in ('src', 'knobs', 'fn', 'desc')}
+    assert [strip(c) for c in recorded if c['src'].startswith('test_')] == [strip(c) for c in T.test_cases()]
+
+
+def test_kernel_form_selection_structural_properties():
+    """seeded random descriptors: ga_*_form rejects exactly what the header's requirements reject (GA_ERR_BAD_ARG); under default knobs
+    no form is named whose hard precondition is false (t256: N % 256 == 0 and K >= 256; pp: K >= NT_PP_MINK; LDS-DMA forms: operand
+    offsets < 2^30; r3: K >= 64); the name of a weight-gradient form gives the bytes ga_wgrad_workspace reports"""
+    import ctypes as C
+    import random
+    from imagenet_models_amd import _lib as L, ops
+    T = _gemm_forms_tool()
+    lib = L.load()
+    rnd = random.Random(20261019)
+    buf = C.create_string_buffer(64)
+    PTR = lambda null=0.0, mis=0.0: 0 if rnd.random() < null else 0x10000 + (rnd.randrange(1, 16) if rnd.random() < mis else 0)
+    dim = lambda: rnd.choice([rnd.randrange(1, 300), 256 * rnd.randrange(1, 64), 6272 << rnd.randrange(6), 65536 + rnd.randrange(140000),
+                              rnd.randrange(1, 3000000), 50176, 73856, 8192, 200704])
+    wid = lambda: rnd.choice([8, 24, 40, 64, 96, 128, 136, 192, 256, 264, 384, 512, 768, 1000, 1536, 2208, 3072, rnd.randrange(1, 3100)])
+    dep = lambda: rnd.choice([8, 48, 64, 72, 96, 192, 200, 256, 328, 384, 512, 520, 768, 1024, 1536, 3072, 8 * rnd.randrange(1, 400),
+                              rnd.randrange(1, 3100)])
+    ld = lambda w: rnd.choice([w] * 8 + [w + 8 * rnd.randrange(9), w + rnd.randrange(1, 8), w + (1 << 20)])
+    taps = {ops.A_PATCH2: 4, ops.A_NEIGH2: 4, ops.A_CONV3: 9, ops.A_CONV3S2: 9, ops.A_STEM4_NCHW: 16}
+
+    def gather(kind):        # (H, W, C, rows per image) of a mostly valid map
+        H, W, Cc = rnd.choice([2, 4, 8, 14, 16, 28, 32, 56, 112, 224, 7]), rnd.choice([2, 4, 8, 16, 28, 32, 48, 56, 112, 224, 5]), \
+            rnd.choice([3, 8, 16, 32, 64, 96, 128, 384])
+        if kind == ops.A_STEM4_NCHW and rnd.random() < 0.9:
+            Cc = 3
+        rows = {ops.A_PATCH2: (H // 2) * (W // 2), ops.A_STEM4_NCHW: (H // 4) * (W // 4), ops.A_CONV3S2: ((H + 1) // 2) * ((W + 1) // 2)}.get(kind, H * W)
+        return H, W, Cc, max(rows, 1)
+
+    seen = set()
+    for i in range(30000):
+        if i % 3:
+            d = L.GemmDesc(M=dim(), N=wid(), K=dep(), batch=rnd.choice([1] * 8 + [2, 6, 0]), dtype=rnd.choice([L.GA_BF16] * 8 + [L.GA_F32, 7]),
+                           a_kind=rnd.choice([ops.A_PLAIN] * 6 + [1, 2, 3, 4, 5, 6]), alpha=rnd.choice([1.0] * 9 + [0.5]),
+                           A=PTR(.01, .01), B=PTR(.01, .01), C=PTR(.01, .01), c_f32=rnd.random() < .05, relu_after=rnd.random() < .04)
+            if d.a_kind in taps:
+                d.a_H, d.a_W, d.a_C, rows = gather(d.a_kind)
+                if rnd.random() < .9:
+                    d.M, d.K = rows * rnd.choice([1, 2, 8, 64, 256]), taps[d.a_kind] * d.a_C
+            d.lda, d.ldb, d.ldc = ld(d.K), ld(d.K), ld(d.N)
+            if rnd.random() < .1:
+                d.c_kind, d.c_H, d.c_W, d.c_C = rnd.choice([ops.C_UNPATCH2] * 9 + [2]), 56, 56, rnd.choice([d.N // 4, 24])
+            epi = rnd.randrange(6)
+            d.bias = PTR(.4, .04)
+            if epi == 1:
+                d.act, d.C2, d.c2_mode = ops.ACT_GELU, PTR(.3, .03), rnd.choice([2, 2, 2, 1, 0])
+            elif epi == 2:
+                d.R, d.ldr, d.rowscale, d.rows_per_scale = PTR(0, .03), ld(d.N), PTR(.5), rnd.choice([49] * 9 + [0])
+            elif epi == 3:
+                d.H, d.ldh, d.h_is_deriv = PTR(0, .03), ld(d.N), rnd.random() < .85
+            elif epi == 4:
+                d.act, d.H, d.ldh, d.R, d.ldr = rnd.randrange(3), PTR(.5), d.N, PTR(.5), d.N
+            d.colsum = PTR(.75)
+            epc = 8 if d.dtype == L.GA_BF16 else 4
+            H, W, Cc = d.a_H, d.a_W, d.a_C
+            ok = bool(d.A and d.B and d.C) and d.batch >= 1 and d.dtype in (L.GA_BF16, L.GA_F32) and not ((d.A | d.B | d.C) & 15) and \
+                d.ldb % epc == 0 and d.K % epc == 0 and \
+                {ops.A_PLAIN: lambda: d.lda % epc == 0,
+                 ops.A_PATCH2: lambda: Cc % epc == 0 and H % 2 == 0 and W % 2 == 0 and d.K == 4 * Cc and d.M % ((H // 2) * (W // 2)) == 0,
+                 ops.A_CONV3: lambda: Cc % epc == 0 and d.K == 9 * Cc and d.M % (H * W) == 0,
+                 ops.A_CONV3S2: lambda: Cc % epc == 0 and d.K == 9 * Cc and d.M % (((H + 1) // 2) * ((W + 1) // 2)) == 0,
+                 ops.A_NEIGH2: lambda: Cc % epc == 0 and d.K == 4 * Cc and d.M % (H * W) == 0,
+                 ops.A_STEM4_NCHW: lambda: Cc == 3 and d.K == 48 and H % 4 == 0 and W % 4 == 0}.get(d.a_kind, lambda: False)() and \
+                ((d.c_C % 8 == 0 and d.N == 4 * d.c_C and not d.c_f32) if d.c_kind == ops.C_UNPATCH2 else d.c_kind == ops.C_PLAIN) and \
+                (not d.H or (d.H & 15 == 0 and d.ldh % 8 == 0)) and (not d.R or (d.R & 15 == 0 and d.ldr % 8 == 0)) and \
+                (not d.C2 or (d.C2 & 15 == 0 and d.c_kind == ops.C_PLAIN and not d.c_f32 and d.c2_mode in (1, 2))) and \
+                (not d.rowscale or d.rows_per_scale > 0) and (d.c_kind != ops.C_PLAIN or d.ldc % 8 == 0)
+            rc = lib.ga_gemm_form(C.byref(d), buf, 64)
+            assert rc == (0 if ok else -1), (rc, ok, T.pack(d), L.last_error())
+            if not ok:
+                continue
+            form = buf.value.decode()
+            kind = form.split(':')[0]
+            seen.add('staged' if kind.startswith('staged') else kind.split('x')[0])
+            fits = d.M * d.lda < 1 << 30 and d.N * d.ldb < 1 << 30
+            assert kind != 't256' or (d.N % 256 == 0 and d.K >= 256 and fits), (form, T.pack(d))
+            assert kind != 'pp' or d.K >= 512, (form, T.pack(d))
+            assert not kind.startswith('dma') or fits, (form, T.pack(d))
+            assert kind not in ('r3', 'r3g') or d.K >= 64, (form, T.pack(d))
+        else:
+            d = L.WgradDesc(M=dim(), N=wid(), K=dep(), batch=rnd.choice([1] * 8 + [2, 0]), dtype=rnd.choice([L.GA_BF16] * 8 + [L.GA_F32, 5]),
+                            x_kind=rnd.choice([ops.A_PLAIN] * 4 + [1, 2, 3, 4, 5, 6]), alpha=1.0, Y=PTR(.01, .01), X=PTR(.01, .01), dW=PTR(.01),
+                            dbias=PTR(.6), split_m=rnd.choice([1, 1, 2, 16, 0]), accumulate=rnd.random() < .7, x_act=rnd.random() < .1)
+            if d.x_kind in taps:
+                d.x_H, d.x_W, d.x_C, rows = gather(d.x_kind)
+                if d.x_kind == ops.A_CONV3S2:
+                    rows = max((d.x_H // 2) * (d.x_W // 2), 1)
+                if rnd.random() < .9:
+                    d.M, d.K = rows * rnd.choice([1, 2, 8, 64, 256]), taps[d.x_kind] * d.x_C
+                if rnd.random() < .7:
+                    d.N = rnd.choice([96, 128]) if d.x_kind == ops.A_STEM4_NCHW else 64
+            d.ldy, d.ldx, d.ldw = ld(d.N), ld(d.K), d.K
+            have_ws = rnd.random() < .8
+            if have_ws:
+                d.workspace, d.ws_bytes = 0x20000, 1 << 50
+            epc = 8 if d.dtype == L.GA_BF16 else 4
+            ok = bool(d.Y and d.X and d.dW) and d.batch >= 1 and d.split_m >= 1 and d.dtype in (L.GA_BF16, L.GA_F32) and not ((d.Y | d.X) & 15) and \
+                d.N % epc == 0 and d.ldy % epc == 0 and \
+                (d.ldx % epc == 0 and d.ldx >= (d.K + epc - 1) // epc * epc if d.x_kind == ops.A_PLAIN else
+                 d.x_C == 3 and d.K == 48 if d.x_kind == ops.A_STEM4_NCHW else
+                 d.x_kind in taps and d.x_C % epc == 0 and d.K == taps[d.x_kind] * d.x_C)
+            rc = lib.ga_wgrad_form(C.byref(d), buf, 64)
+            assert rc == (0 if ok else -1), (rc, ok, T.pack(d), L.last_error())
+            if not ok:
+                continue
+            form = buf.value.decode()
+            part = form.split(':')
+            seen.add(part[0])
+            per_wg = {'conv3_wgrad_direct': 64 * 576, 'conv3s2_wgrad_direct': 64 * 576, 'conv0_wgrad_direct': 64 * 72, 'stem4_wgrad_direct': d.N * 49}
+            need = lib.ga_wgrad_workspace(C.byref(d))
+            if not have_ws:
+                assert part[0] in ('tn', 'tn2', 'tn2p') and part[-1] != 'partials', form
+            elif part[0] in per_wg:
+                assert need == int(part[1][3:]) * per_wg[part[0]] * 4, (form, need)
+            elif part[0] == 'tn':
+                assert need == 0, (form, need)
+            else:
+                assert need == (d.batch * int(part[1][5:]) * d.N * d.K * 4 if part[2] == 'partials' else 0), (form, need)
+    assert seen >= {'r3', 'r3g', 'dma256', 'pp', 't256', 'dma128', 'big', 'staged', 'tn', 'tn2', 'tn2p', 'stem4_wgrad_direct'}, seen

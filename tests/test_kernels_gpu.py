@@ -307,8 +307,12 @@ def test_stem_conv_layernorm_one_pass(geom):
 @pytest.mark.parametrize('shape', [(70000, 384, 96), (66000, 192, 200), (65600, 768, 384), (70000, 96, 384), (66000, 512, 328),
                                    (33000, 1536, 768), (40100, 264, 520), (12500, 3072, 768), (50200, 384, 1536)])
 def test_gemm_lds_dma_form_bf16(shape, form, knobs):
-    """large-M bf16 launches take the 256-row LDS-DMA form (ragged M, ragged K slab, 96- and 128-wide column tiles):
-    plain + column sums, fc1 (GELU and GELU' outputs), fc2 (row scale + residual), dgrad2 (x stored GELU' + sums)"""
+    """large-M bf16 launches (ragged M, ragged K slab, 96- and 128-wide column tiles) under the knobs that once forced each NT form:
+    plain + column sums, fc1 (GELU and GELU' outputs), fc2 (row scale + residual), dgrad2 (x stored GELU' + sums).
+    Since the ring form became the default, forcing another form does not switch its heuristic off and it is tried first, so of the
+    36 launches of a parameter (9 shapes x 4 epilogues) the named form takes: dma256 2 (the plain epilogue of 40100x264x520 and
+    12500x3072x768), dma128 0, t256 0 (both: ring 34, pp 1, staged-96 1), pp 13, r3 36; the rest run on the ring form
+    (tools/gemm_forms.py --coverage).  Reaching the named forms needs NT_R3=0 beside these knobs: a follow-up."""
     ops = _imp()
     if form == 'dma256':
         knobs(NT_DMA=2)      # every eligible launch, not only the shapes the heuristic picks
