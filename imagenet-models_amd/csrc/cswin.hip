@@ -130,8 +130,11 @@ __global__ __launch_bounds__(128) void cswin_attn_fwd_simple(const ga_cswin_attn
 // =================================================================================================================
 // generic backward: dq, dk, dv (incl. the LePE transpose) of one (image, window, head)
 // LDS: q k v do [128][HD+1] fp32; P, dS [N][N+1] fp32
+// RC (the stripes whose two planes do not fit the 160 KiB of LDS, see attn_lds): ONE plane [N][N+1] that ends as dS, and
+// lse [128]; the query phase computes dO.v twice instead of storing it, the key phase recomputes P = exp(s - lse) from
+// the same fmaf chain that gave s in the query phase.
 // =================================================================================================================
-template <typename T, int HD>
+template <typename T, int HD, bool RC>
 __global__ __launch_bounds__(128) void cswin_attn_bwd_simple(const ga_cswin_attn_desc d, const void* dout_, void* dqkv_) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const WinGeom g = win_geom(d, blockIdx.x);
@@ -141,7 +144,8 @@ __global__ __launch_bounds__(128) void cswin_attn_bwd_simple(const ga_cswin_attn
     float* vs = ks + 128 * LD;
     float* gs = vs + 128 * LD;           // dO
     float* P = gs + 128 * LD;
-    float* dS = P + N * LS;
+    float* dS = RC ? P : P + N * LS;
+    float* lse = P + N * LS;             // RC only
     const int t = threadIdx.x;
     const T* qkv = reinterpret_cast<const T*>(d.qkv);
     const T* dout = reinterpret_cast<const T*>(dout_);
@@ -167,39 +171,72 @@ __global__ __launch_bounds__(128) void cswin_attn_bwd_simple(const ga_cswin_attn
             q[c] = qs[t * LD + c] * d.scale;
             go[c] = gs[t * LD + c];
         }
-        float m = -3.0e38f;
-        for (int j = 0; j < N; ++j) {
-            float s = 0.f, dp = 0.f;
-#pragma unroll
-            for (int c = 0; c < HD; ++c) {
-                s = fmaf(q[c], ks[j * LD + c], s);
-                dp = fmaf(go[c], vs[j * LD + c], dp);
-            }
-            P[t * LS + j] = s;
-            dS[t * LS + j] = dp;
-            m = fmaxf(m, s);
-        }
-        float l = 0.f;
-        for (int j = 0; j < N; ++j) {
-            const float p = __expf(P[t * LS + j] - m);
-            P[t * LS + j] = p;
-            l += p;
-        }
-        const float inv = 1.f / l;
-        float delta = 0.f;
-        for (int j = 0; j < N; ++j) {
-            const float p = P[t * LS + j] * inv;
-            P[t * LS + j] = p;
-            delta = fmaf(p, dS[t * LS + j], delta);
-        }
         float dq[HD];
 #pragma unroll
         for (int c = 0; c < HD; ++c) dq[c] = 0.f;
-        for (int j = 0; j < N; ++j) {
-            const float ds = P[t * LS + j] * (dS[t * LS + j] - delta);
-            dS[t * LS + j] = ds;
+        if constexpr (RC) {
+            float m = -3.0e38f;
+            for (int j = 0; j < N; ++j) {
+                float s = 0.f;
 #pragma unroll
-            for (int c = 0; c < HD; ++c) dq[c] = fmaf(ds, ks[j * LD + c], dq[c]);
+                for (int c = 0; c < HD; ++c) s = fmaf(q[c], ks[j * LD + c], s);
+                dS[t * LS + j] = s;
+                m = fmaxf(m, s);
+            }
+            float l = 0.f, delta = 0.f;
+            for (int j = 0; j < N; ++j) {
+                float dp = 0.f;
+#pragma unroll
+                for (int c = 0; c < HD; ++c) dp = fmaf(go[c], vs[j * LD + c], dp);
+                const float p = __expf(dS[t * LS + j] - m);
+                dS[t * LS + j] = p;
+                l += p;
+                delta = fmaf(p, dp, delta);
+            }
+            const float inv = 1.f / l;
+            delta *= inv;
+            for (int j = 0; j < N; ++j) {
+                float dp = 0.f;
+#pragma unroll
+                for (int c = 0; c < HD; ++c) dp = fmaf(go[c], vs[j * LD + c], dp);
+                const float ds = dS[t * LS + j] * inv * (dp - delta);
+                dS[t * LS + j] = ds;
+#pragma unroll
+                for (int c = 0; c < HD; ++c) dq[c] = fmaf(ds, ks[j * LD + c], dq[c]);
+            }
+            lse[t] = m + __logf(l);
+        } else {
+            float m = -3.0e38f;
+            for (int j = 0; j < N; ++j) {
+                float s = 0.f, dp = 0.f;
+#pragma unroll
+                for (int c = 0; c < HD; ++c) {
+                    s = fmaf(q[c], ks[j * LD + c], s);
+                    dp = fmaf(go[c], vs[j * LD + c], dp);
+                }
+                P[t * LS + j] = s;
+                dS[t * LS + j] = dp;
+                m = fmaxf(m, s);
+            }
+            float l = 0.f;
+            for (int j = 0; j < N; ++j) {
+                const float p = __expf(P[t * LS + j] - m);
+                P[t * LS + j] = p;
+                l += p;
+            }
+            const float inv = 1.f / l;
+            float delta = 0.f;
+            for (int j = 0; j < N; ++j) {
+                const float p = P[t * LS + j] * inv;
+                P[t * LS + j] = p;
+                delta = fmaf(p, dS[t * LS + j], delta);
+            }
+            for (int j = 0; j < N; ++j) {
+                const float ds = P[t * LS + j] * (dS[t * LS + j] - delta);
+                dS[t * LS + j] = ds;
+#pragma unroll
+                for (int c = 0; c < HD; ++c) dq[c] = fmaf(ds, ks[j * LD + c], dq[c]);
+            }
         }
         T* o = dqkv + row * d.ldq + g.ch;
 #pragma unroll
@@ -211,7 +248,16 @@ __global__ __launch_bounds__(128) void cswin_attn_bwd_simple(const ga_cswin_attn
 #pragma unroll
     for (int c = 0; c < HD; ++c) dk[c] = dv[c] = 0.f;
     for (int i = 0; i < N; ++i) {
-        const float p = P[i * LS + t], ds = dS[i * LS + t];
+        float p;
+        if constexpr (RC) {
+            float s = 0.f;
+#pragma unroll
+            for (int c = 0; c < HD; ++c) s = fmaf(qs[i * LD + c] * d.scale, ks[t * LD + c], s);
+            p = __expf(s - lse[i]);
+        } else {
+            p = P[i * LS + t];
+        }
+        const float ds = dS[i * LS + t];
 #pragma unroll
         for (int c = 0; c < HD; ++c) {
             dv[c] = fmaf(p, gs[i * LD + c], dv[c]);
@@ -942,6 +988,29 @@ bool use_mfma(const ga_cswin_attn_desc* d) {
     return true;
 }
 
+// LDS bytes of the form that serves d (forward, or backward), the ONE place where the demand is computed: the launches
+// take their dynamic LDS size from it and refuse from it, before any hipFuncSetAttribute or launch, what exceeds kLdsMax.
+// *recompute (generic backward only): the two [N][N+1] planes P and dS do not fit next to the four operand tiles (head_dim 32:
+// N > 109, head_dim 16: N > 126), so the one-plane form of cswin_attn_bwd_simple runs.  With it every accepted stripe
+// (N <= 128, head_dim <= 32) fits forward and backward: at most 134 144 B.
+constexpr size_t kLdsMax = 160 * 1024;
+
+size_t attn_lds(const ga_cswin_attn_desc* d, bool bwd, bool* recompute = nullptr) {
+    int nmax = 0;
+    for (int i = 0; i < d->nbranch; ++i) nmax = std::max(nmax, d->Hs[i] * d->Ws[i]);
+    if (recompute) *recompute = false;
+    if (use_mfma(d)) {
+        const size_t tile = nmax <= 64 ? AT<4>::TILE : AT<7>::TILE, kp = nmax <= 64 ? AT<4>::KP : AT<7>::KP;
+        return bwd ? 4 * tile + 4096 + 2 * kp * sizeof(float) + 16 : 3 * tile + 4096 + 16;
+    }
+    const size_t hd = d->C / d->heads, plane = (size_t)nmax * (nmax + 1);
+    if (!bwd) return (3 * 128 * (hd + 1) + plane) * sizeof(float);
+    const size_t two = (4 * 128 * (hd + 1) + 2 * plane) * sizeof(float);
+    if (two <= kLdsMax) return two;
+    if (recompute) *recompute = true;
+    return (4 * 128 * (hd + 1) + plane + 128) * sizeof(float);
+}
+
 template <typename K> bool set_lds(K kern, size_t bytes) {
     return bytes <= 65536 ||
            hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
@@ -959,17 +1028,15 @@ extern "C" int ga_cswin_attn_fwd(const ga_cswin_attn_desc* d, ga_stream_t stream
     const int hd = d->C / d->heads;
     int nmax = 0;
     for (int i = 0; i < d->nbranch; ++i) nmax = std::max(nmax, d->Hs[i] * d->Ws[i]);
+    const size_t lds = attn_lds(d, false);
+    GA_REQUIRE(lds <= kLdsMax, "ga_cswin_attn_fwd: %zu B of LDS needed", lds);
     if (use_mfma(d)) {
-        if (nmax <= 64) {
-            const size_t lds = 3 * AT<4>::TILE + 4096 + 16;
+        if (nmax <= 64)
             hipLaunchKernelGGL(cswin_attn_fwd_mfma<4>, dim3(items), dim3(256), lds, s, *d, items);
-        } else {
-            const size_t lds = 3 * AT<7>::TILE + 4096 + 16;
+        else
             hipLaunchKernelGGL(cswin_attn_fwd_mfma<7>, dim3(items), dim3(256), lds, s, *d, items);
-        }
         return ga_check_launch("ga_cswin_attn_fwd");
     }
-    const size_t lds = ((size_t)3 * 128 * (hd + 1) + (size_t)nmax * (nmax + 1)) * sizeof(float);
 #define GA_FWD(T, HD)                                                                                              \
     do {                                                                                                           \
         GA_REQUIRE(set_lds(cswin_attn_fwd_simple<T, HD>, lds), "ga_cswin_attn_fwd: cannot reserve %zu B of LDS", lds); \
@@ -1004,21 +1071,24 @@ extern "C" int ga_cswin_attn_bwd(const ga_cswin_attn_desc* d, const void* dout, 
     const int hd = d->C / d->heads;
     int nmax = 0;
     for (int i = 0; i < d->nbranch; ++i) nmax = std::max(nmax, d->Hs[i] * d->Ws[i]);
+    bool rc = false;
+    const size_t lds = attn_lds(d, true, &rc);
+    GA_REQUIRE(lds <= kLdsMax, "ga_cswin_attn_bwd: %zu B of LDS needed", lds);
     if (use_mfma(d)) {
-        if (nmax <= 64) {
-            const size_t lds = 4 * AT<4>::TILE + 4096 + 2 * AT<4>::KP * sizeof(float) + 16;
+        if (nmax <= 64)
             hipLaunchKernelGGL(cswin_attn_bwd_mfma<4>, dim3(items), dim3(256), lds, s, *d, dout, dqkv, (float*)lepe_ws, items);
-        } else {
-            const size_t lds = 4 * AT<7>::TILE + 4096 + 2 * AT<7>::KP * sizeof(float) + 16;
+        else
             hipLaunchKernelGGL(cswin_attn_bwd_mfma<7>, dim3(items), dim3(256), lds, s, *d, dout, dqkv, (float*)lepe_ws, items);
-        }
         return ga_check_launch("ga_cswin_attn_bwd");
     }
-    const size_t lds = ((size_t)4 * 128 * (hd + 1) + (size_t)2 * nmax * (nmax + 1)) * sizeof(float);
+#define GA_BWD1(T, HD, RC)                                                                                             \
+    do {                                                                                                               \
+        GA_REQUIRE(set_lds(cswin_attn_bwd_simple<T, HD, RC>, lds), "ga_cswin_attn_bwd: cannot reserve %zu B of LDS", lds); \
+        hipLaunchKernelGGL((cswin_attn_bwd_simple<T, HD, RC>), dim3(items), dim3(128), lds, s, *d, dout, dqkv);        \
+    } while (0)
 #define GA_BWD(T, HD)                                                                                              \
     do {                                                                                                           \
-        GA_REQUIRE(set_lds(cswin_attn_bwd_simple<T, HD>, lds), "ga_cswin_attn_bwd: cannot reserve %zu B of LDS", lds); \
-        hipLaunchKernelGGL((cswin_attn_bwd_simple<T, HD>), dim3(items), dim3(128), lds, s, *d, dout, dqkv);        \
+        if (rc) GA_BWD1(T, HD, true); else GA_BWD1(T, HD, false);                                                  \
     } while (0)
     if (d->dtype == GA_BF16) {
         if (hd == 8) GA_BWD(bf16_t, 8); else if (hd == 16) GA_BWD(bf16_t, 16); else GA_BWD(bf16_t, 32);
@@ -1026,6 +1096,7 @@ extern "C" int ga_cswin_attn_bwd(const ga_cswin_attn_desc* d, const void* dout, 
         if (hd == 8) GA_BWD(float, 8); else if (hd == 16) GA_BWD(float, 16); else GA_BWD(float, 32);
     }
 #undef GA_BWD
+#undef GA_BWD1
     return ga_check_launch("ga_cswin_attn_bwd");
 }
 
@@ -1034,6 +1105,8 @@ extern "C" int ga_cswin_lepe_wgrad(const ga_cswin_attn_desc* d, const void* dout
     if (int rc = check_desc(d, "ga_cswin_lepe_wgrad")) return rc;
     GA_REQUIRE(dout && dw0 && db0 && (d->nbranch == 1 || (dw1 && db1)), "ga_cswin_lepe_wgrad: null gradient");
     GA_REQUIRE(d->C / 8 <= 256 && (d->C / d->nbranch) % 8 == 0, "ga_cswin_lepe_wgrad: C=%d unsupported", d->C);
+    GA_REQUIRE(aligned16(dout) && d->ldo >= d->C && d->ldo % (d->dtype == GA_BF16 ? 8 : 4) == 0,
+               "ga_cswin_lepe_wgrad: dout alignment / ldo (8-element loads)");
     const int C8 = d->C / 8, rpb = 256 / C8;
     const long rows = (long)d->B * d->reso * d->reso;
     const int grid = (int)std::max<long>(1, std::min<long>(1024, (rows + 4L * rpb - 1) / (4L * rpb)));

@@ -479,7 +479,10 @@ int ga_clip_grad_f32(float* g, int64_t n, const float* sumsq, float limit, int m
  *   branch i owns channels [i*C/nbranch, (i+1)*C/nbranch) of each block, heads/nbranch heads, stripes Hs[i] x Ws[i];
  *   out[b, t, ch] = softmax_j((q_t * scale) . k_j) v_j + conv3x3_depthwise(v)(t)   over the tokens j of t's stripe,
  *   the 3x3 (lepe_w[i]: fp32 [C/nbranch][9] = get_v.weight, lepe_b[i]) zero padded at the STRIPE border.
- *   head_dim in {8, 16, 32}; Hs*Ws <= 128.  bf16 with head_dim 32 runs on MFMA, everything else on a generic fp32 form.
+ *   head_dim in {8, 16, 32}; Hs*Ws <= 128, for fwd AND bwd at every head_dim and dtype (both take their LDS size from one host
+ *   function and refuse with GA_ERR_BAD_ARG what exceeds 160 KiB; no accepted shape does: where the generic backward's two
+ *   [N][N+1] score planes do not fit -- head_dim 32: N > 109, head_dim 16: N > 126 -- it keeps one and recomputes P).
+ *   bf16 with head_dim 32 and Hs*Ws <= 112 runs on MFMA, everything else on a generic fp32 form.
  * bwd: dqkv [B*L][ldq] = d(q | k | v) from dout [B*L][ldo]  (dv includes the LePE transpose).  With a caller-owned `lepe_ws` of
  *   ga_cswin_attn_bwd_workspace(d) bytes (16-byte aligned; 0 = this shape runs the generic form, pass NULL) the kernel also
  *   leaves the per-(window, head) partial LePE weight gradients there from the tiles it already holds in LDS;
