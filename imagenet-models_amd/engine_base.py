@@ -261,7 +261,8 @@ class EngineBase:
         """SyncBatchNorm (GA/train.py:449-455, --sync-bn): sum a small fp32 statistics vector over the ranks, enqueued on the lane the
         plan call runs on (ga_allreduce_bucket through the communicator convert_sync_batchnorm() attached to the model)"""
         c = self.sync_bn
-        plan._add('ga_allreduce_bucket', (c.handle, ops._ptr(t), t.numel(), GA_F32, 1.0, None, 0), label, keep=(t, c))
+        plan.record('ga_allreduce_bucket', c.handle, t, t.numel(), GA_F32, 1.0, None, 0, label=label)
+        plan.keep.append(c)       # the handle is a host value: the communicator behind it must outlive the plan
 
     def _bn_finalize(self, pre, bn, n, C):
         if self.sync_bn is not None and self.training:       # batch statistics over the GLOBAL batch: sums of all ranks, n x world
@@ -283,8 +284,8 @@ class EngineBase:
             # torch.nn.SyncBatchNorm's backward: the parameter gradients take the LOCAL column sums (the gradient all-reduce averages
             # them later), so they are accumulated right here -- not deferred to the stage flush --; then the two sums that enter dx
             # are summed over the ranks in place
-            Bk._add('ga_axpy_f32', (ops._ptr(self.grad(pre + 'weight')), ops._ptr(s2), 1.0, c_real or C), pre + 'dgamma', keep=(s2,))
-            Bk._add('ga_axpy_f32', (ops._ptr(self.grad(pre + 'bias')), ops._ptr(s1), 1.0, c_real or C), pre + 'dbeta', keep=(s1,))
+            Bk.record('ga_axpy_f32', self.grad(pre + 'weight'), s2, 1.0, c_real or C, label=pre + 'dgamma')
+            Bk.record('ga_axpy_f32', self.grad(pre + 'bias'), s1, 1.0, c_real or C, label=pre + 'dbeta')
             self._sync_allreduce(Bk, s1, pre + 'sync.s1')
             self._sync_allreduce(Bk, s2, pre + 'sync.s2')
             n = rows * self.sync_bn.world

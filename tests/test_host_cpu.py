@@ -13,6 +13,23 @@ import torch.multiprocessing as mp
 from conftest import ROOT
 
 
+_C_CLASS = {'int': 'int', 'int64_t': 'i64', 'float': 'f32', 'double': 'f64', 'size_t': 'u64', 'uint64_t': 'u64'}
+
+
+def _c_class(ctype):
+    """class of a C type as the header spells it: every pointer and handle is 'ptr'"""
+    ctype = re.sub(r'\bconst\b', '', ctype).strip()
+    return 'ptr' if '*' in ctype or ctype in ('ga_stream_t', 'ga_comm_t') else _C_CLASS[ctype]
+
+
+def _py_class(typ):
+    """... and of a ctypes type of _lib"""
+    import ctypes as C
+    if typ in (C.c_void_p, C.c_char_p) or issubclass(typ, C._Pointer):
+        return 'ptr'
+    return {C.c_int: 'int', C.c_int64: 'i64', C.c_float: 'f32', C.c_double: 'f64', C.c_size_t: 'u64', C.c_uint64: 'u64'}[typ]
+
+
 def test_library_exports_every_declared_symbol():
     from imagenet_models_amd import _lib
     lib = _lib.load()
@@ -23,6 +40,15 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), f'{name} declared in include/gaext.h but not exported by libgaext.so'
     assert sorted(_lib.exported_symbols()) == declared, 'ctypes signature table out of sync with the header'
     assert lib.ga_version() >= 100
+    # every prototype: argument count, the class of each argument (pointer / handle, int, int64_t, float, double, 64-bit unsigned)
+    # and of the return value against _SIGS
+    protos = re.findall(r'^\s*(int|size_t)\s+(ga_\w+)\s*\(([^)]*)\)\s*;', re.sub(r'/\*.*?\*/', '', hdr, flags=re.S), flags=re.M)
+    assert sorted(p[1] for p in protos) == declared
+    for ret, name, params in protos:
+        params = [] if params.strip() in ('', 'void') else [re.sub(r'\w+$', '', p.strip()) for p in params.split(',')]
+        argtypes, restype = _lib._SIGS[name]
+        assert [_c_class(p) for p in params] == [_py_class(t) for t in argtypes], name
+        assert _c_class(ret) == _py_class(restype), name
 
 
 def test_tuning_knobs_are_a_table_not_the_environment():
@@ -59,26 +85,38 @@ def test_library_never_allocates_device_memory():
 
 
 def test_descriptor_structs_match_header_field_order():
+    import ctypes as C
     from imagenet_models_amd import _lib
     hdr = open(os.path.join(ROOT, 'include', 'gaext.h')).read()
 
     def fields(struct_name):
+        """(name, class, array length or 0) of every field, in order"""
         end = hdr.index('} ' + struct_name + ';')
         body = hdr[hdr.rindex('typedef struct {', 0, end) + len('typedef struct {'):end]
         body = re.sub(r'/\*.*?\*/', '', body, flags=re.S)
-        names = []
+        out = []
         for decl in body.split(';'):
             decl = decl.strip()
             if not decl:
                 continue
-            decl = re.sub(r'^(const\s+)?(void|float|int64_t|int)\s*\*?', '', decl).strip()
-            for part in decl.split(','):
-                names.append(part.strip().lstrip('*').strip())
-        return names
+            base, stars, rest = re.match(r'^((?:const\s+)?\w+)\s*(\**)\s*(.*)$', decl, flags=re.S).groups()
+            for part in rest.split(','):
+                ptr, name, n = re.match(r'^\s*(\**)\s*(\w+)\s*(?:\[(\d+)\])?\s*$', part).groups()
+                out.append((name, _c_class(base + stars + ptr), int(n or 0)))
+        return out
 
-    for cname, cls in (('ga_gemm_desc', _lib.GemmDesc), ('ga_wgrad_desc', _lib.WgradDesc),
-                       ('ga_wprep_desc', _lib.WprepDesc), ('ga_wunfold_desc', _lib.WunfoldDesc)):
-        assert fields(cname) == [f[0] for f in cls._fields_], cname
+    def py_fields(cls):
+        return [(name, _py_class(typ._type_), typ._length_) if issubclass(typ, C.Array) else (name, _py_class(typ), 0)
+                for name, typ in cls._fields_]
+
+    structs = (('ga_gemm_desc', _lib.GemmDesc), ('ga_wgrad_desc', _lib.WgradDesc), ('ga_wprep_desc', _lib.WprepDesc),
+               ('ga_wunfold_desc', _lib.WunfoldDesc), ('ga_small_desc', _lib.SmallDesc), ('ga_cswin_attn_desc', _lib.CswinAttnDesc),
+               ('ga_mlp_desc', _lib.MlpDesc), ('ga_mlp_bwd_desc', _lib.MlpBwdDesc), ('ga_small_linear_desc', _lib.SmallLinearDesc),
+               ('ga_attn_desc', _lib.AttnDesc))
+    assert len(structs) == hdr.count('typedef struct {') == len([c for c in vars(_lib).values()
+                                                                  if isinstance(c, type) and issubclass(c, C.Structure)])
+    for cname, cls in structs:
+        assert fields(cname) == py_fields(cls), cname
 
 
 def test_registry_and_factories():

@@ -74,8 +74,8 @@ class Recorder(ops.Plan):
         super().__init__()
         self.src, self.kn, self.cases = src, knobs, cases
 
-    def _add(self, fname, args, label=None, keep=()):
-        self.cases.append(dict(src=self.src, knobs=self.kn, fn=fname, desc=pack(args[0]._obj)))
+    def record(self, fname, d, label=None):
+        self.cases.append(dict(src=self.src, knobs=self.kn, fn=fname, desc=pack(d)))
 
     def _want_workspace(self, nbytes, patch):
         patch(0x1000, nbytes)
