@@ -37,10 +37,6 @@ class ConvNeXt(FlatModel):
         from .engine_convnext import ConvNeXtEngine
         return ConvNeXtEngine(self, batch, training, mode)
 
-    def grad_groups(self):
-        return [('heads', ('head.', 'norm.')), ('stage3', ('stages.3.', 'downsample_layers.3.')),
-                ('stage2', ('stages.2.', 'downsample_layers.2.')), ('stage1', ('stages.1.', 'downsample_layers.1.'))]
-
     def forward(self, x, pre_logits=False):
         assert not pre_logits
         return super().forward(x)[0]

@@ -34,8 +34,9 @@ class ConvNeXtTrunk:
 
     # parameter names of the ConvNeXt trunk: GA-ConvNeXt follows timm's ConvNeXt (ga_convnext.py:86-137,356-359), MAP-ConvNeXt
     # the FB one (map_convnext.py:16-83) -- same arithmetic, different module names
+    # `stage`: the prefixes of everything whose gradient is final once stage i's backward (blocks, then its downsample) is recorded
     NAMES = dict(stem_conv='stem.0.', stem_ln='stem.1.', ds_ln='stages.{i}.downsample.0.', ds_conv='stages.{i}.downsample.1.',
-                 block='stages.{i}.blocks.{j}.', dw='conv_dw.', fc1='mlp.fc1.', fc2='mlp.fc2.')
+                 block='stages.{i}.blocks.{j}.', dw='conv_dw.', fc1='mlp.fc1.', fc2='mlp.fc2.', stage=('stages.{i}.',))
 
     def _build_trunk(self):
         """stem + the four ConvNeXt stages; returns (feats [(x, res)], taps, stage_in [(x, H)], stem output)"""
@@ -313,10 +314,8 @@ class ConvNeXtTrunk:
                                  seed[i - 1], dprev, self.grad(pln + 'weight'), self.grad(pln + 'bias'), Mp, d[i - 1],
                                  False, dt, label=pre + 'lnb')
                 dy = dprev
-            if self.async_wgrad:
-                Bk.join_async()
-            Bk.flush(f'stage{i}.')
-            Bk.mark(f'stage{i}')  # gradients of stages.i (incl. its downsample) are final
+            # gradients of stage i (incl. its downsample) are final; stage 0's stay with the stem's, under the end of the plan
+            self._seal(f'stage{i}', *([p.format(i=i) for p in nm['stage']] if i > 0 else ()), flush=f'stage{i}.')
         # stem
         M0 = dy.shape[0]
         sc, sl = nm['stem_conv'], nm['stem_ln']
@@ -362,7 +361,7 @@ class GroupMlp:
 
     def _unpad_all(self):
         """real part of every padded parameter gradient back into the parameter's gradient; call AFTER the flush of the heads'
-        deferred weight-unfold jobs (they write the padded gradients) and before the 'heads' mark"""
+        deferred weight-unfold jobs (they write the padded gradients) and before the 'heads' mark (_seal(..., then=self._unpad_all))"""
         for name, g in self.pgrad.items():
             _, kind, a = self.ppad[name]
             if kind == 'copy':
@@ -1205,15 +1204,12 @@ class GAEngine(ConvNeXtTrunk, GAHeads, EngineBase):
         self._block_bwd(h['blk'], dg1, dg0)
 
     def _build_backward(self, feats, taps, stage_in, x4, M4, ctot):
-        Bk, cfg = self.bwd, self.cfg
+        cfg = self.cfg
         dx4 = self._build_heads_backward(x4, M4)
         dcat = self.tmp('dcat', (M4, ctot))
         self._bottleneck_bwd(dx4, dcat)
-        if self.async_wgrad:
-            Bk.join_async()
-        Bk.flush('heads.')
-        self._unpad_all()
-        Bk.mark('heads')      # every gradient of stages.4 / gram_* / ga / fc is final here
+        self._seal('heads', 'stages.4.', 'gram_contraction.', 'gram_layer.', 'gram_embedding.', 'ga.', 'fc.', flush='heads.',
+                   then=self._unpad_all)
         # aggregate backward -> gradient seeds of the stage outputs / taps
         seeds = self._aggregate_bwd(dcat, ctot, 14)
         ntap = len(taps)

@@ -14,6 +14,9 @@ A family is `class XEngine(<builders...>, EngineBase)`: the builders (engine.Con
 engine_vit.ViTBlocks, engine_pit.PiTTrunk) are stateless classes of recording methods -- no __init__, attributes created by their own
 build methods only -- and the family fills in the hooks `_drop_path_rates`, `_build` and, where it needs more gradient scratch,
 `_arena_extra`.  The constructor runs `_build()` and then the tail every plan ends with (`_finish`).
+
+Where a group of gradients is complete the family says so with `_seal(mark, prefixes...)`: the backward plan's mark at which
+TrainStep may start reducing them (`grad_groups()`, `backward_to(mark)`); `grad()` refuses a sealed name for the rest of the build.
 """
 import contextlib
 import os
@@ -65,6 +68,8 @@ class EngineBase:
         self._chain = None       # (lane, first image, end image) while a forward chain is being recorded
         self._bwd_seq = 0        # trunk blocks recorded on the backward plan so far
         self._pre_dyz = {}       # block prefix -> DropPath-scaled dy already written by the block before it (backward order)
+        self._sealed = {}        # backward-plan mark -> parameter-name prefixes whose gradients are final there, in sealing order
+        self._bwd_pos = 0        # how far backward_to() has run the backward plan since the last forward
         self.sync_bn = getattr(model, 'sync_bn_comm', None)      # FlatModel.convert_sync_batchnorm(comm): --sync-bn (GA/train.py:449-455)
         self.W = {}
         self.weights_dirty = True
@@ -196,7 +201,34 @@ class EngineBase:
         return self.arena[off:off + n].view(shape)
 
     def grad(self, name):
+        """gradient buffer of a parameter, for a launch that is recorded NOW: a call recorded after the seal of its group would
+        write (or read) the gradient after TrainStep has started reducing it"""
+        for mark, prefixes in self._sealed.items():
+            if name.startswith(prefixes):
+                raise RuntimeError(f'gradient of {name} requested after mark {mark!r} sealed {prefixes}: it is final there')
         return self.P[name].grad
+
+    def _seal(self, mark, *prefixes, flush, then=None):
+        """the gradients of the parameters under `prefixes` are final from here on: wait for the asynchronous lane, emit the deferred
+        small jobs under label `flush`, record `then()` (what must sit between flush and mark) and set `mark`.  flush=None: the
+        segment defers nothing and has nothing on the asynchronous lane beyond what Plan.run_range joins at the end of every range,
+        so neither join nor flush is recorded.  No prefixes: a mark nothing is claimed at"""
+        Bk = self.bwd
+        if flush is not None:
+            if self.async_wgrad:
+                Bk.join_async()
+            Bk.flush(flush)
+        if then is not None:
+            then()
+        Bk.mark(mark)
+        if prefixes:
+            self._sealed[mark] = prefixes
+
+    def grad_groups(self):
+        """[(backward-plan mark, parameter-name prefixes whose gradients are final at that mark)] in backward-completion order;
+        parameters under no prefix are final at the end of backward.  trainer.make_buckets cuts the flat gradient buffer by it
+        into all-reduce buckets that start while the rest of backward still runs.  An eval engine seals nothing: []"""
+        return list(self._sealed.items())
 
     def sample_drop_path(self):
         """fresh per-sample Bernoulli(keep)/keep factors for every stochastic-depth site (timm DropPath): one launch of
@@ -377,6 +409,7 @@ class EngineBase:
                         e.weights_dirty = True
         if self.training and self.dp_scale and not self.fixed_masks:
             self.sample_drop_path()
+        self._bwd_pos = 0
         self.fwd.run()
         if self.training:
             self.m.count_training_forward()     # num_batches_tracked: host-side count, written on state_dict()
@@ -401,12 +434,13 @@ class EngineBase:
         self.loss_cfg = (lam, kind, smoothing, grad_scale, dense, bce_threshold)
 
     def forward_loss(self, x, target, lam, kind=0, smoothing=0.0, grad_scale=1.0, bce_threshold=-1.0):
-        """forward + loss (+ dlogits) without autograd; follow with backward_range()/bwd.run(). Returns the loss buffer.
+        """forward + loss (+ dlogits) without autograd; follow with backward_to(mark) ... backward_to('end'), or bwd.run().
+        Returns the loss buffer.
         target: class indices (B,) or a dense (B, NC) floating-point target"""
         dense = target.dim() == 2
         if self.loss_cfg != (lam, kind, smoothing, grad_scale, dense, bce_threshold):
             self.build_loss(lam, kind, smoothing, grad_scale, dense, bce_threshold)
-        self.forward(x)
+        self.forward(x)              # (resets backward_to's position)
         self.target_buf.copy_(target, non_blocking=True)
         self.loss_plan.run()
         return self.loss_buf
@@ -419,3 +453,12 @@ class EngineBase:
                 p = Plan(eager=True)
                 p.cast_from_f32(dlogits.contiguous().float(), self.dlogits, self.dlogits.numel(), self.dt)
         self.bwd.run()
+
+    def backward_to(self, mark):
+        """run the backward plan from where the previous call stopped (the start, after a forward) up to `mark`; 'end': the end of
+        the plan.  Nothing runs when the position is already there or past it"""
+        bwd = self.bwd
+        stop = len(bwd.calls) if mark == 'end' else bwd.marks[mark]
+        if stop > self._bwd_pos:
+            bwd.run_range(self._bwd_pos, stop)
+            self._bwd_pos = stop

@@ -29,5 +29,5 @@ class ConvNeXtEngine(FBConvNeXtTrunk, EngineBase):
                              self.grad('norm.bias'), B, C, False, dt, label='head.lnb')
             seed3 = self.buf('head.seed3', (B * HW, C))
             Bk.rows_bcast(dpool, seed3, B, HW, C, 1.0 / HW, dt, label='head.poolb')
-            Bk.mark('heads')
+            self._seal('heads', 'head.', 'norm.', flush=None)       # nothing deferred, the classifier's weight gradient joined by the range's end
             self._build_trunk_backward({3: seed3, 2: None, 1: None, 0: None}, [], [], feats, stage_in)

@@ -468,11 +468,8 @@ class CSWinEngine(GAHeads, EngineBase):
             Bk.gemm(dc5, W[lp + 'conv.weight.T'], dcat, M4, ctot, cur, dt, ldb=pad8(cur), label=lp + 'dg')
         else:
             self._bottleneck_bwd(dx4, dcat)
-        if self.async_wgrad:
-            Bk.join_async()
-        Bk.flush('heads.')
-        self._unpad_all()
-        Bk.mark('heads')      # every gradient of stage5 / gram_* / ga / fc is final here
+        self._seal('heads', 'stage5.', 'gram_contraction.', 'gram_layer.', 'gram_embedding.', 'ga.', 'fc.', flush='heads.',
+                   then=self._unpad_all)
         # aggregate backward -> gradient seeds of the stage outputs / taps
         seeds = self._aggregate_bwd(dcat, ctot, 14)
         ntap = len(taps)
@@ -499,10 +496,8 @@ class CSWinEngine(GAHeads, EngineBase):
                 dprev = self.tmp(f'dprev{si}', (B * Hp * Hp, d[si - 1]))
                 self._conv3s2_ln_bwd(self.merges[si], dy, dprev, seed=seed[si - 1])
                 dy = dprev
-            if self.async_wgrad:
-                Bk.join_async()
-            Bk.flush(f'stage{si + 1}.')
-            Bk.mark(f'stage{si}')   # gradients of trunk stage si+1 (incl. its merge) are final
+            # gradients of trunk stage si+1 (incl. its merge) are final; stage1's stay with the stem's, under the end of the plan
+            self._seal(f'stage{si}', *((f'stage{si + 1}.', f'merge{si}.') if si > 0 else ()), flush=f'stage{si + 1}.')
         # ---------------- deep stem ----------------
         S = self.stem
         sp = 'stage1_conv_embed.'

@@ -28,7 +28,8 @@ from .ops import Plan
 class FBConvNeXtTrunk(ConvNeXtTrunk):
     """the ConvNeXt trunk under the FB module names and DropPath schedule of map_convnext.py (MAP-ConvNeXt, plain ConvNeXt)"""
     NAMES = dict(stem_conv='downsample_layers.0.0.', stem_ln='downsample_layers.0.1.', ds_ln='downsample_layers.{i}.0.',
-                 ds_conv='downsample_layers.{i}.1.', block='stages.{i}.{j}.', dw='dwconv.', fc1='pwconv1.', fc2='pwconv2.')
+                 ds_conv='downsample_layers.{i}.1.', block='stages.{i}.{j}.', dw='dwconv.', fc1='pwconv1.', fc2='pwconv2.',
+                 stage=('stages.{i}.', 'downsample_layers.{i}.'))
 
     def _drop_path_rates(self):
         """map_convnext.py:85 -- linspace over sum(depths) of the four stages"""
@@ -536,12 +537,11 @@ class MAPHead(GroupMlp):
             Bk.wgrad(dc, ms['cat'], self.grad(mp + '0.weight'), M4, L, ctot, dt, label=mp + 'wg')
         dcat = self.tmp('dcat', (M4, ctot))
         Bk.gemm(dc, W[mp + '0.weight.T'], dcat, M4, ctot, L, dt, ldb=pad8(L), label=mp + 'dg')
-        if self.async_wgrad:
-            Bk.join_async()
-        Bk.flush('heads.')
-        assert not self.pgrad, 'padded parameter gradients are not copied back on this path'
-        Bk.mark('heads')      # every gradient of head.* is final here
+        self._seal('heads', self.HP, flush='heads.', then=self._no_padded_grads)      # every gradient of head.* is final here
         return dcat
+
+    def _no_padded_grads(self):
+        assert not self.pgrad, 'padded parameter gradients are not copied back on this path'
 
     # ------------------------------------------------------------------------------------------
     def forward(self, x):

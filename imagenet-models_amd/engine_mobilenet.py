@@ -104,10 +104,7 @@ class MobileNetEngine(MAPHead, EngineBase):
             dpool = self._linear_head_bwd(self.pool, 'fc.2.', C4, 'head.dpool')
             dy = self.buf('head.seed', (M4, C4))
             Bk.rows_bcast(dpool, dy, B, H4 * H4, C4, 1.0 / (H4 * H4), dt, label='fc.poolb')
-            if self.async_wgrad:
-                Bk.join_async()
-            Bk.flush('heads.')
-            Bk.mark('heads')
+            self._seal('heads', 'fc.', flush='heads.')
         # input gradients ping-pong between two buffers per shape; what the asynchronous weight gradients read (the gradients
         # behind the BatchNorms) is kept per layer, so no later launch of the main lane overwrites it
         flip = 0
@@ -116,10 +113,7 @@ class MobileNetEngine(MAPHead, EngineBase):
                 flip ^= 1
                 dy = self._conv_dw_bwd(u, dy, self.tmp(f'dx{flip}', (B * u['H'] * u['H'], u['cin'])))
             if i > 0:
-                if self.async_wgrad:
-                    Bk.join_async()
-                Bk.flush(f'stage{i}.')
-                Bk.mark(f'stage{i}')
+                self._seal(f'stage{i}', f'layers.{i}.', flush=f'stage{i}.')
         # stem: weight gradient only
         st, sp = self.stem, 'layers.0.0.'
         dc = self.buf(sp + 'dc', (st['M'], st['C']))

@@ -121,10 +121,7 @@ class PiTTrunk(ViTBlocks):
                 dy = dprev
                 # transformers.s and pools.(s-1) are final only after the pooling conv's weight gradient (asynchronous lane) and the
                 # deferred unfold jobs of the stage's blocks: join + flush BEFORE the mark the gradient buckets key on
-                if self.async_wgrad:
-                    Bk.join_async()
-                Bk.flush(f'stage{s + 1}.')
-                Bk.mark(f'stage{s + 1}')
+                self._seal(f'stage{s + 1}', f'transformers.{s}.', f'pools.{s - 1}.', flush=f'stage{s + 1}.')
         # dy: gradient wrt x0 from stage 0; x0 is also feature 0
         if seeds[0] is not None:
             Bk.copy2d(seeds[0], w0 * w0 * dims[0], dy, w0 * w0 * dims[0], B, w0 * w0 * dims[0], dt, accumulate=True, label='feat.0.b')
@@ -164,8 +161,5 @@ class PiTEngine(PiTTrunk, EngineBase):
             dpool = self._linear_head_bwd(pool, 'head.', C, 'head.dpool')
             seed = self.buf('head.seed', (B * N, C))
             Bk.token_gap_bwd(dpool, seed, B, N, C, dt, label='head.poolb')
-            if self.async_wgrad:
-                Bk.join_async()
-            Bk.flush('heads.')
-            Bk.mark('heads')
+            self._seal('heads', 'head.', flush='heads.')
             self._build_pit_trunk_backward([None, None, None, seed], K0)

@@ -192,10 +192,7 @@ class ResNetEngine(MAPHead, EngineBase):
             if li > 0:
                 M, C = dy.shape
                 Bk.affine_act(dy, None, None, seeds[li], dy, M, C, False, dt, label=f'layer{li}.seed')
-            if self.async_wgrad:
-                Bk.join_async()
-            Bk.flush(f'layer{li + 1}.')
-            Bk.mark(f'layer{li + 1}')      # gradients of layer{li+1}.* are final
+            self._seal(f'layer{li + 1}', f'layer{li + 1}.', flush=f'layer{li + 1}.')
         # max pool -> adds into the multi-scale gradient of the stem output
         S, C0, H1 = self.stem, self.cfg['stem_ch'], self.img // 2
         M1 = B * H1 * H1

@@ -246,10 +246,7 @@ class MAPViTEngine(ViTBlocks, MAPHead, EngineBase):
             if i == depth // 2:
                 # every gradient of blocks[depth // 2 :] and of the final norm must be FINAL at the mark (TrainStep all-reduces
                 # the group's slice from here on): wait for the weight-gradient lane, emit the deferred unfold jobs
-                if self.async_wgrad:
-                    Bk.join_async()
-                Bk.flush('stage2.')
-                Bk.mark('stage2')
+                self._seal('stage2', 'norm.', *(f'blocks.{k}.' for k in range(depth // 2, depth)), flush='stage2.')
         # embedding: dtok, d(cls_token), d(pos_embed); patch projection weight gradient
         dtok = self.tmp('dtok', (Mp, C))
         Bk.vit_embed_bwd(dxs[cur], dtok, self.grad('cls_token'), self.grad('pos_embed'), B, Np, C, dt, label='embedb')

@@ -143,12 +143,6 @@ class FlatModel(nn.Module):
         self._engines = {}
         return self
 
-    def grad_groups(self):
-        """[(backward-plan mark, parameter-name prefixes whose gradients are final at that mark)] in backward-completion
-        order; parameters matched by no group are final at the end of backward.  Used to cut the flat gradient buffer into
-        all-reduce buckets that start while the rest of backward still runs (trainer.make_buckets)."""
-        return []
-
     def load_state_dict(self, state_dict, strict=True, assign=False):
         if self._flat is not None:
             own = self.state_dict()

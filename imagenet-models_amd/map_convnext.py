@@ -185,10 +185,6 @@ class MAP_ConvNeXt(FlatModel):
         from .engine_map import MAPEngine
         return MAPEngine(self, batch, training, mode)
 
-    def grad_groups(self):
-        return [('heads', ('head.',)), ('stage3', ('stages.3.', 'downsample_layers.3.')),
-                ('stage2', ('stages.2.', 'downsample_layers.2.')), ('stage1', ('stages.1.', 'downsample_layers.1.'))]
-
     def forward(self, x, pre_logits=False):
         """eval: list of n_groups logits; train: list of [org_out, avg_out] (map.py:519-537)"""
         assert not pre_logits, 'pre_logits (MAP/validate.py --logit-extract) is not on the hot path'

@@ -72,9 +72,6 @@ class MAP_PiT(FlatModel):
         from .engine_pit import MAPPiTEngine
         return MAPPiTEngine(self, batch, training, mode)
 
-    def grad_groups(self):
-        return [('heads', ('head.',)), ('stage3', ('transformers.2.', 'pools.1.')), ('stage2', ('transformers.1.', 'pools.0.'))]
-
     def forward(self, x, pre_logits=False):
         """eval: list of n_groups logits; train: list of [org_out, avg_out] (map.py:519-537)"""
         assert not pre_logits

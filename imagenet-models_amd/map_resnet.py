@@ -95,10 +95,6 @@ class MAP_ResNet(FlatModel):
         from .engine_resnet import ResNetEngine
         return ResNetEngine(self, batch, training, mode)
 
-    def grad_groups(self):
-        return [('heads', ('head.',)), ('layer4', ('layer4.',)), ('layer3', ('layer3.',)), ('layer2', ('layer2.',)),
-                ('layer1', ('layer1.',))]
-
     def forward(self, x, pre_logits=False):
         """eval: list of 4 logits; train: list of 4 [org_out, avg_out] (map.py:519-537)"""
         assert not pre_logits, 'pre_logits is not on the hot path'

@@ -77,10 +77,6 @@ class MAP_ViT(FlatModel):
         from .engine_vit import MAPViTEngine
         return MAPViTEngine(self, batch, training, mode)
 
-    def grad_groups(self):
-        d = self.cfg['depth']
-        return [('heads', ('head.',)), ('stage2', ('norm.',) + tuple(f'blocks.{i}.' for i in range(d // 2, d)))]
-
     def forward(self, x, pre_logits=False):
         """eval: list of n_groups logits; train: list of [org_out, avg_out] (map.py:519-537)"""
         assert not pre_logits

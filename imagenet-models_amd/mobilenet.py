@@ -75,10 +75,6 @@ class MobileNetV1(FlatModel):
         from .engine_mobilenet import MobileNetEngine
         return MobileNetEngine(self, batch, training, mode)
 
-    def grad_groups(self):
-        return [('heads', ('fc.',)), ('stage4', ('layers.4.',)), ('stage3', ('layers.3.',)), ('stage2', ('layers.2.',)),
-                ('stage1', ('layers.1.',))]
-
     def forward(self, x, pre_logits=False):
         """plain: (B, n_classes) logits; MAP: [logits] (one group, no self-distillation token)"""
         assert not pre_logits, 'pre_logits is not on the hot path'

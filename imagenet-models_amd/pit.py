@@ -70,9 +70,6 @@ class PiT(FlatModel):
         from .engine_pit import PiTEngine
         return PiTEngine(self, batch, training, mode)
 
-    def grad_groups(self):
-        return [('heads', ('head.',)), ('stage3', ('transformers.2.', 'pools.1.')), ('stage2', ('transformers.1.', 'pools.0.'))]
-
     def forward(self, x, pre_logits=False):
         assert not pre_logits
         return super().forward(x)[0]

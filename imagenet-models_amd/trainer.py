@@ -6,8 +6,8 @@ buckets while the remaining backward runs -> fused flat optimizer.
 Replaces NativeDDP (GA/train.py:514): its 25 MB reverse-registration-order bucket reducer, its per-forward broadcast of
 the BatchNorm buffers from rank 0 (`broadcast_buffers`, off with --no-ddp-bb :283) and, with `distribute_bn`, timm's
 epoch-end running-statistics reduction (:665-674).  The flat gradient layout follows the parameter registration order,
-so the parameters of one trunk stage / of the heads are a few contiguous slices; `FlatModel.grad_groups()` says which
-name prefixes are final at which mark of the backward plan."""
+so the parameters of one trunk stage / of the heads are a few contiguous slices; the training engine's `grad_groups()` says
+which name prefixes it sealed at which mark of its backward plan, and `backward_to(mark)` runs the plan up to there."""
 import torch
 import torch.distributed as dist
 
@@ -116,9 +116,10 @@ class TrainStep:
         # stream while backward goes on -- possible whenever nothing needs ALL gradients first (norm clipping, LAMB's norms, the
         # non-finite guard).  Off by default: on one GPU the 0.26 ms AdamW pass hidden this way costs more in segmented issue
         # and HBM contention than it saves (ga_convnext_tiny_768, B = 256: 24.9 ms with, 24.7 without, same box)
+        groups = self.eng.grad_groups()
         self.overlap_opt = (overlap_optimizer and getattr(optimizer, 'supports_ranges', False) and clip_grad is None
-                            and not nan_guard and bool(model.grad_groups()))
-        self.buckets = make_buckets(st, model.grad_groups(), bucket_elems) if (self.bucketed or self.overlap_opt) else []
+                            and not nan_guard and bool(groups))
+        self.buckets = make_buckets(st, groups, bucket_elems) if (self.bucketed or self.overlap_opt) else []
         self.opt_stream = torch.cuda.Stream() if (self.overlap_opt and comm is None) else None
         self._opt_done = torch.cuda.Event() if self.overlap_opt else None
         self.last_loss_sum = torch.zeros(1, device=self.flat_g.device) if nan_guard else None
@@ -155,32 +156,36 @@ class TrainStep:
                 p.clip_grad_f32(self.flat_g, n, self.gnorm_sq, clip_grad, 1)
             self.clip_plan = p
 
-    def _backward_with_updates(self, bwd):
+    def _reduce_via(self):
+        """how a bucketed step sums a gradient slice over the ranks: 'comm' (the library's RCCL entry points), 'dist'
+        (torch.distributed) or None (one rank, no process group: the segments run, nothing is reduced)"""
+        if not self.bucketed:
+            return None
+        if self.comm is not None:
+            return 'comm'
+        return 'dist' if (self.world > 1 or dist.is_initialized()) else None
+
+    def _backward_with_updates(self):
         """backward in bucket segments; behind each segment, on a side stream: [all-reduce of the bucket,] optimizer update of
         the bucket, zeroing of its gradients.  The main stream rejoins before the step returns."""
-        opt = self.opt
+        opt, eng = self.opt, self.eng
         opt.step_begin()                                  # hyper-parameters reach the device on the main stream, ahead of every event
         main = torch.cuda.current_stream()
         side = self.comm.stream if self.comm is not None else self.opt_stream
-        reduce = self.bucketed and (self.comm is not None or self.world > 1 or dist.is_initialized())
-        pos = 0
+        via = self._reduce_via()
         for mark, a, b in self.buckets:
-            stop = len(bwd.calls) if mark == 'end' else bwd.marks[mark]
-            if stop > pos:
-                bwd.run_range(pos, stop)
-                pos = stop
+            eng.backward_to(mark)
             ev = torch.cuda.Event()
             ev.record(main)
             side.wait_event(ev)
-            if reduce and self.comm is not None:
+            if via == 'comm':
                 self.comm.allreduce(self.flat_g[a:b])
-            elif reduce:
+            elif via == 'dist':
                 work = dist.all_reduce(self.flat_g[a:b], group=self.pg, async_op=True)
                 with torch.cuda.stream(side):
                     work.wait()
             opt.step_range(a, b, side.cuda_stream)
-        if pos < len(bwd.calls):
-            bwd.run_range(pos, len(bwd.calls))
+        eng.backward_to('end')
         self._opt_done.record(side)
         main.wait_event(self._opt_done)
         opt.step_end()
@@ -210,37 +215,33 @@ class TrainStep:
             # float tensor coming back from it would make the engine skip the normalisation
             x, target = self.mixup_fn(eng._normalize_u8(x), target)
         loss = eng.forward_loss(x, target, self.lam, self.kind, self.smoothing, scale, self.bce_threshold)
-        bwd = eng.bwd
         if self.overlap_opt and last_micro:
-            self._backward_with_updates(bwd)
+            self._backward_with_updates()
             self.micro += 1
             return loss
         if self.bucketed and last_micro:
-            works, pos = [], 0
+            works, via = [], self._reduce_via()
             main = torch.cuda.current_stream()
             for mark, a, b in self.buckets:
-                stop = len(bwd.calls) if mark == 'end' else bwd.marks[mark]
-                if stop > pos:
-                    bwd.run_range(pos, stop)
-                    pos = stop
-                if self.comm is not None:            # RCCL through the C ABI, on the comm stream, behind this segment
+                eng.backward_to(mark)
+                if via == 'comm':                     # RCCL through the C ABI, on the comm stream, behind this segment
                     self.comm.after(main)
                     self.comm.allreduce(self.flat_g[a:b])
-                elif self.world > 1 or dist.is_initialized():
+                elif via == 'dist':
                     works.append(dist.all_reduce(self.flat_g[a:b], group=self.pg, async_op=True))
             if self.nan_guard:                        # one float beside the last bucket: sum over ranks of the scaled loss
                 self.last_loss_sum.copy_(loss.reshape(1), non_blocking=True)
-                if self.comm is not None:
+                if via == 'comm':
                     self.comm.after(main)
                     self.comm.allreduce(self.last_loss_sum)
-                elif self.world > 1 or dist.is_initialized():
+                elif via == 'dist':
                     works.append(dist.all_reduce(self.last_loss_sum, group=self.pg, async_op=True))
             if self.comm is not None:
                 self.comm.join(main)
             for w in works:
                 w.wait()
         else:
-            bwd.run()
+            eng.bwd.run()
         self.micro += 1
         if last_micro:
             if self.clip_plan is not None:

@@ -58,12 +58,9 @@ def main():
     assert all(covered[i][1] == covered[i + 1][0] for i in range(len(covered) - 1)), covered   # exact partition
     eng = step.eng
     eng.forward_loss(x, y, -0.8, 0, 0.0, 1.0 / world)
-    works, pos = [], 0
+    works = []
     for mark, a, b in step.buckets:
-        stop = len(eng.bwd.calls) if mark == 'end' else eng.bwd.marks[mark]
-        if stop > pos:
-            eng.bwd.run_range(pos, stop)
-            pos = stop
+        eng.backward_to(mark)
         works.append(dist.all_reduce(step.flat_g[a:b], async_op=True))
     for w in works:
         w.wait()

@@ -153,7 +153,7 @@ def test_optimizer_update_by_slices_is_bit_identical_to_the_whole_step(opt_name)
         m, O = _small_model()
         opt = A.create_optimizer_v2(m, opt=opt_name, lr=1e-2, momentum=0.9, weight_decay=0.05)
         st = m.flat_state()
-        buckets = make_buckets(st, m.grad_groups(), 50_000)
+        buckets = make_buckets(st, m.engine(2, True).grad_groups(), 50_000)
         assert len(buckets) >= 4 and sum(b - a for _, a, b in buckets) == st['total']
         for it in range(2):
             st['grads'].copy_(torch.randn(st['total'], generator=torch.Generator().manual_seed(it)).cuda())

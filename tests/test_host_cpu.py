@@ -168,6 +168,12 @@ def _small():
     return A.GA_ConvNeXt(num_classes=40, depths=(1, 1, 6, 1, 1), dims=(16, 32, 64, 128, 128), gram_dim=32, dim_embed=64)
 
 
+# what _small()'s training engine seals (EngineBase.grad_groups(); there is no engine on the CPU): tests/test_grad_marks_gpu.py
+# asserts that the engine reports exactly this
+GA_CONVNEXT_GROUPS = [('heads', ('stages.4.', 'gram_contraction.', 'gram_layer.', 'gram_embedding.', 'ga.', 'fc.')),
+                      ('stage3', ('stages.3.',)), ('stage2', ('stages.2.',)), ('stage1', ('stages.1.',))]
+
+
 def test_flat_layout_and_buckets_partition_the_gradient_buffer():
     from imagenet_models_amd.trainer import TrainStep
     m = _small()
@@ -184,7 +190,7 @@ def test_flat_layout_and_buckets_partition_the_gradient_buffer():
         assert (off < n_decay) == (not m.no_weight_decay_param(n, p))
     from imagenet_models_amd.trainer import make_buckets
     for cap in (8 << 20, 50000):     # one bucket per run / runs cut into <= 50k-element all-reduces
-        buckets = make_buckets(st, m.grad_groups(), cap)
+        buckets = make_buckets(st, GA_CONVNEXT_GROUPS, cap)
         cover = sorted((a, b) for _, a, b in buckets)
         assert cover[0][0] == 0 and cover[-1][1] == total
         for (a0, b0), (a1, b1) in zip(cover, cover[1:]):
@@ -193,9 +199,9 @@ def test_flat_layout_and_buckets_partition_the_gradient_buffer():
         # backward-completion order: the heads' slices first (the end of the decay segment), marks never go backwards
         assert buckets[0][0] == 'heads' and any(mk == 'heads' and b == n_decay for mk, a, b in buckets)
         marks = [mk for mk, _, _ in buckets]
-        order = [g for g, _ in m.grad_groups()] + ['end']
+        order = [g for g, _ in GA_CONVNEXT_GROUPS] + ['end']
         assert [order.index(mk) for mk in marks] == sorted(order.index(mk) for mk in marks)
-        owner = {n: next((g for g, pre in m.grad_groups() if n.startswith(tuple(pre))), 'end') for n in st['slices']}
+        owner = {n: next((g for g, pre in GA_CONVNEXT_GROUPS if n.startswith(tuple(pre))), 'end') for n in st['slices']}
         for n, (off, k) in st['slices'].items():
             assert all(mk == owner[n] for mk, a, b in buckets if a < off + k and off < b), n
     k_off = st['slices']['ga.0.attn.k.weight'][0]
@@ -212,7 +218,7 @@ def _gloo_worker(rank, world, port, q):
     m = _small()
     m._flatten()
     st = m.flat_state()
-    buckets = make_buckets(st, m.grad_groups(), 60000)
+    buckets = make_buckets(st, GA_CONVNEXT_GROUPS, 60000)
     g = torch.Generator().manual_seed(100 + rank)
     local = torch.randn(st['total'], generator=g)
     st['grads'].copy_(local / world)          # TrainStep folds 1/world into the loss gradient scale

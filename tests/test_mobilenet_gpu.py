@@ -6,7 +6,7 @@ written by tools/gen_golden_mobilenet.py from the REAL reference classes (MAP/mo
   * bf16 throughput mode against the fp32 mode: eval logits from the fixture's running statistics (gated), and the same train step
     (errors reported; loss gated): at B = 4 the train-mode BatchNorms of the 27-layer trunk -- and in the MAP head the bp_reduction
     BatchNorm over the 4 batch rows -- amplify bf16 rounding far beyond what the eval pass sees;
-  * a bucketed world-1 TrainStep (force_buckets, NativeComm) equal to the plain step: the backward-plan marks of grad_groups();
+  * a bucketed world-1 TrainStep (force_buckets, NativeComm) equal to the plain step: the backward-plan marks the engine seals;
   * two TrainSteps and an eval through create_model at the default 1000 classes.
 fp32 gates: logits / loss 1e-3, gradient norms 1e-2 per tensor (first 16 elements of each tensor 2e-2 of its norm), running
 statistics 1e-3."""
