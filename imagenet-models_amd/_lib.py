@@ -210,6 +210,9 @@ _SIGS = {
     'ga_input_collate': ([vp, i32, vp, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp, i32, i32, C.c_uint64, C.c_uint64, vp],
                          i32),
     'ga_mixup_target_elem': ([vp, vp, i32, i32, vp, C.c_double, vp], i32),
+    'ga_rand_augment': ([vp, vp, vp, C.c_size_t, i32, i32, i32, i32, vp, i32, vp, vp], i32),
+    'ga_rand_augment_work_bytes': ([i32, i32, i32, i32, i32], C.c_size_t),
+    'ga_rand_augment_check_table': ([vp, i32], i32),
     'ga_mixup_batch': ([vp, vp, i32, i32, i32, i32, C.c_double, i32, i32, i32, i32, i32, vp], i32),
     'ga_mixup_target': ([vp, vp, i32, i32, C.c_double, C.c_double, vp], i32),
     'ga_agc_clip': ([vp, vp, vp, i32, f32, f32, vp], i32),

@@ -793,6 +793,17 @@ class Plan:
         self.record('ga_input_collate', x, u8, out, B, CH, H, W, m, s, mix, boxes, int(max_count), int(mode), _u64(seed), _u64(offset),
                     label=label)
 
+    def rand_augment(self, x, out, work, table, n_layers, fill, label=None):
+        """timm RandAugment on a uint8 (B, 3, H, W) batch, out of place: table = device uint8 (B, n_layers, 64) of rows
+        {kind, interp, iarg, farg, m[6]} (include/gaext.h), work = device uint8 scratch of rand_augment_work_bytes() bytes (None
+        without layers), fill = the CH bytes a pixel without a source takes"""
+        B, CH, H, W = x.shape
+        self.record('ga_rand_augment', x, out, work, C.c_size_t(_nbytes(work)), B, CH, H, W, table, int(n_layers),
+                    (C.c_ubyte * CH)(*[int(v) for v in fill]), label=label)
+
+    def rand_augment_work_bytes(self, B, CH, H, W, n_layers):
+        return int(self.lib.ga_rand_augment_work_bytes(B, CH, H, W, int(n_layers)))
+
     def mixup_target_elem(self, target, out, NC, lam, smoothing, label=None):
         """dense target of per-sample lams: lam = device fp32 (B,)"""
         self.record('ga_mixup_target_elem', target, out, target.numel(), NC, lam, float(smoothing), label=label)

@@ -66,7 +66,7 @@ class TrainStep:
     def __init__(self, model, optimizer, batch, lam=0.0, loss='ce', smoothing=0.0, grad_accumulation=1,
                  process_group=None, clip_grad=None, clip_mode='norm', broadcast_buffers=True, bucket_elems=BUCKET_ELEMS,
                  mixup_fn=None, bce_target_thresh=None, comm=None, force_buckets=False, nan_guard=False,
-                 overlap_optimizer=False, random_erasing=None, collate_mixup=None):
+                 overlap_optimizer=False, random_erasing=None, collate_mixup=None, auto_augment=None):
         """The input stage has two orders.
         Default (mixup_fn / random_erasing): normalise -> erase -> mixup -> engine, all in fp32.  random_erasing is an
         imagenet_models_amd.RandomErasing (for a uint8 batch the erase pass IS the normalisation, ga_input_erase, so the batch is
@@ -79,6 +79,9 @@ class TrainStep:
         MAP/train.py:383): mixup / cutmix on the uint8 batch at collate time, each blended value rounded back to uint8, then the
         normalisation, then random_erasing LAST on the mixed image -- one HIP pass (ga_input_collate).  It needs a uint8 batch,
         takes this step's random_erasing into the fused pass, and excludes mixup_fn.
+        auto_augment (opt-in): an imagenet_models_amd.RandAugment -- timm's --aa rand-..., which timm applies to the cropped uint8
+        image ahead of fast_collate: it runs FIRST, on the uint8 batch (ga_rand_augment), and hands its uint8 result to whichever
+        input stage is configured above.  It needs a uint8 batch.
         comm: an imagenet_models_amd.NativeComm -- the gradient buckets (and the BatchNorm-buffer broadcast) go through the
         library's own RCCL entry points (ga_allreduce_bucket on a side stream) instead of torch.distributed.
         force_buckets: take the segmented-backward + bucketed-reduction path even with one rank (tests: the real collective
@@ -97,6 +100,7 @@ class TrainStep:
         self.mixup_fn = mixup_fn
         self.collate_mixup = collate_mixup
         self.random_erasing = random_erasing
+        self.auto_augment = auto_augment
         self.bce_threshold = -1.0 if bce_target_thresh is None else float(bce_target_thresh)
         self.accum = grad_accumulation
         self.pg = process_group
@@ -204,6 +208,10 @@ class TrainStep:
                 dist.broadcast(self.flat_buffers, 0, group=self.pg)
         # the reference divides the loss by grad_accumulation (train.py:750); DDP averages over ranks
         scale = 1.0 / (self.accum * self.world)
+        if self.auto_augment is not None:
+            if x.dtype != torch.uint8:
+                raise TypeError(f'TrainStep(auto_augment=...) augments the uint8 batch of the loader, got {x.dtype}')
+            x = self.auto_augment(x)
         if self.collate_mixup is not None:
             if x.dtype != torch.uint8:
                 raise TypeError(f'TrainStep(collate_mixup=...) mixes the uint8 batch of the loader, got {x.dtype}')

@@ -622,6 +622,51 @@ int ga_input_collate(const void* x, int x_is_u8, float* out, int B, int CH, int 
                      const int32_t* mix, const int32_t* boxes, int max_count, int mode, uint64_t seed, uint64_t offset,
                      ga_stream_t stream);
 int ga_mixup_target_elem(const int64_t* target, float* out, int B, int NC, const float* lam, double smoothing, ga_stream_t stream);
+/* timm RandAugment (--aa rand-mN-mstd0.5-inc1, every recipe of MAP/train_with_script.py:13-19) on the uint8 NCHW batch of timm's
+ * fast_collate, ahead of ga_input_collate / ga_input_erase / ga_u8_normalize: out-of-place, CH == 3, every byte equal to what PIL
+ * gives for the call timm makes.  ops: DEVICE table [B][n_layers] of 64-byte rows, drawn by the host (imagenet_models_amd.RandAugment):
+ *   { int32 kind, int32 interp, int32 iarg, fp32 farg, double m[6] }
+ * Layer l+1 of a sample reads the COMPLETE output of layer l.  n_layers == 0 and a row of kind 0 copy the sample; the kernel treats
+ * an unknown kind as 0 (ga_rand_augment_check_table refuses one on the host, before the table is staged).
+ *   kind 0 none
+ *        1 autocontrast  per channel: lo / hi = lowest / highest occupied histogram bin; hi <= lo: identity; else
+ *                        lut[i] = clamp(int(i * s + (-lo * s)), 0, 255), s = 255.0 / (hi - lo), in double, truncated toward zero
+ *        2 equalize      per channel, histogram h: step = (sum(h) - h[last occupied bin]) / 255 (integer); <= 1 occupied bin or
+ *                        step == 0: identity; else n = step / 2; for i = 0..255: lut[i] = min(255, n / step); n += h[i]
+ *        3 invert        255 - a
+ *        4 posterize     a & ~(2^(8 - iarg) - 1);  iarg >= 8: identity;  iarg 0: 0
+ *        5 solarize      a < iarg ? a : 255 - a
+ *        6 solarize_add  a < 128 ? min(255, a + iarg) : a
+ *        7 color         blend(gray, a, farg)        gray = (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16 of the pixel
+ *        8 contrast      blend(mean, a, farg)        mean = int(sum(gray over the image) / (H * W) + 0.5), the division in double
+ *        9 brightness    blend(0, a, farg)
+ *       10 sharpness     blend(smooth, a, farg)      smooth = the 3x3 kernel (1,1,1,1,5,1,1,1,1): the fp32 sum / 13, + 0.5, clipped and
+ *                                                    truncated; the border row and column are the image's own
+ *       11 affine        m, interp (PIL's codes: 0 nearest, 2 bilinear, 3 bicubic); a pixel without a source takes fill[c]
+ *   blend(d, a, f) = d + f * (a - d) in fp32, the product and the sum separately rounded (no FMA); <= 0 -> 0, >= 255 -> 255, else
+ *   TRUNCATED.
+ *   affine, output pixel (x, y), bilinear / bicubic, all in double without contraction:
+ *     xin = m0 (x + 0.5) + m1 (y + 0.5) + m2,  yin = m3 (x + 0.5) + m4 (y + 0.5) + m5;  outside 0 <= xin < W, 0 <= yin < H: fill
+ *     x' = xin - 0.5, x0 = floor(x'), dx = x' - x0 (likewise y); neighbour indices are clamped to the image
+ *     bilinear: L(v1, v2, d) = v1 + (v2 - v1) d along x for two rows, then along y
+ *     bicubic, taps x0-1 .. x0+2: p1 = v2; p2 = -v1 + v3; p3 = 2 (v1 - v2) + v3 - v4; p4 = -v1 + v2 - v3 + v4;
+ *               p1 + d (p2 + d (p3 + d p4)) along x for four rows, then along y
+ *     result <= 0 -> 0, >= 255 -> 255, else truncated
+ *   affine, nearest -- PIL leaves the double path here, and so does this:
+ *     m1 == 0 and m3 == 0: xo = m2 + m0 * 0.5, then x additions of m0 (each rounded); source column int(xo), none if xo < 0 or >= W;
+ *                          rows likewise from m5 + m4 * 0.5 and m4
+ *     otherwise 16.16 fixed point, F(v) = floor(v * 65536 + 0.5): source column (F(m2 + m0 * 0.5 + m1 * 0.5) + F(m1) y + F(m0) x) >> 16,
+ *                          row (F(m5 + m3 * 0.5 + m4 * 0.5) + F(m4) y + F(m3) x) >> 16, none outside the image
+ * fill: HOST array of CH bytes.  work: caller-owned, ga_rand_augment_work_bytes(...) bytes: 1 KiB of per-sample statistics (the
+ * three LUTs, the grey mean) and the ping-pong image(s) between layers (none for n_layers <= 1, one for 2, two beyond).
+ * No allocation, no host synchronisation, no floating-point atomics (integer LDS histograms only): deterministic.
+ * GA_ERR_BAD_ARG, nothing launched: out == x, CH != 3, H*W % 4 != 0, H or W >= 32768, x / out off the 4-byte or ops / work off the
+ * 16-byte grid, work_bytes too small, n_layers < 0; from ga_rand_augment_check_table (a HOST copy of `rows` table rows): a kind
+ * outside 0..11 or an interp other than 0, 2, 3. */
+int ga_rand_augment(const void* x, void* out, void* work, size_t work_bytes, int B, int CH, int H, int W, const void* ops, int n_layers,
+                    const uint8_t* fill, ga_stream_t stream);
+size_t ga_rand_augment_work_bytes(int B, int CH, int H, int W, int n_layers);
+int ga_rand_augment_check_table(const void* ops_host, int rows);
 /* adaptive gradient clipping (timm adaptive_clip_grad, clip_mode 'agc'): units = int64 {offset, length} pairs into the flat fp32
  * parameter / gradient buffers (a row of a >= 2-d parameter or a whole <= 1-d one); per unit
  * g *= max(|p|, eps) * clip_factor / max(|g|, 1e-6) where |g| exceeds max(|p|, eps) * clip_factor */

@@ -63,6 +63,11 @@ parser.add_argument('--remode', type=str, default='pixel', help='Random erase mo
 parser.add_argument('--recount', type=int, default=1, help='Random erase count (default: 1)')
 parser.add_argument('--resplit', action='store_true', default=False, help='Do not random erase first (clean) augmentation split '
                     '(inert here: the reference splits only under --aug-splits, which is not built)')
+# RandAugment on the device (MAP/train.py --aa; every recipe of MAP/train_with_script.py runs rand-mN-mstd0.5-inc1)
+parser.add_argument('--aa', type=str, default=None, metavar='NAME', help='Use AutoAugment policy, timm\'s "rand-m9-mstd0.5-inc1" form '
+                    '(RandAugment only; applied on the device to the uint8 batch, ahead of every other input stage). (default: None)')
+parser.add_argument('--train-interpolation', type=str, default='random', help='Training interpolation of the geometric RandAugment ops '
+                    '(random, bilinear, bicubic, nearest; default: "random")')
 parser.add_argument('--drop-path', type=float, default=None)
 parser.add_argument('--grad-accumulation', type=int, default=1)
 parser.add_argument('--GA_lam', type=float, default=0)
@@ -182,6 +187,12 @@ def main():
                          "it is not built ('batch', 'pair' or 'elem')")
     if args.mixup_mode not in ('batch', 'pair', 'elem'):
         raise SystemExit(f"train.py: --mixup-mode {args.mixup_mode!r}: 'batch', 'pair' or 'elem'")
+    if args.aa:
+        from imagenet_models_amd.rand_augment import RandAugment
+        try:
+            RandAugment(args.aa, interpolation=args.train_interpolation)
+        except ValueError as e:
+            raise SystemExit(f'train.py: --aa / --train-interpolation: {e}')
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', str(args.local_rank)))
@@ -244,15 +255,17 @@ def main():
     if args.reprob > 0.:
         random_erasing = A.RandomErasing(probability=args.reprob, mode=args.remode, max_count=args.recount, num_splits=0,
                                          seed=args.seed + rank)
+    # RandAugment as timm's create_transform builds it: fill = the rounded dataset mean, the interpolation of the geometric ops
+    auto_augment = A.RandAugment(args.aa, interpolation=args.train_interpolation) if args.aa else None
     step_fn = A.TrainStep(model, opt, args.batch_size, lam=lam, loss='bce' if args.bce_loss else 'ce',
                           smoothing=args.smoothing, grad_accumulation=args.grad_accumulation,
                           clip_grad=args.clip_grad, clip_mode=args.clip_mode, broadcast_buffers=not args.no_ddp_bb,
                           mixup_fn=mixup_fn, bce_target_thresh=args.bce_target_thresh, comm=comm, random_erasing=random_erasing,
-                          collate_mixup=collate_mixup)
+                          collate_mixup=collate_mixup, auto_augment=auto_augment)
     model_ema = A.ModelEma(model, args.model_ema_decay) if args.model_ema else None
     img = getattr(model, 'cfg', {}).get('img_size', 224)
     loader = SyntheticLoader(args.batch_size, args.steps_per_epoch, model.num_classes, args.seed + rank, 'cuda', img,
-                             uint8=collate_mixup is not None)
+                             uint8=collate_mixup is not None or auto_augment is not None)
     eval_loader = SyntheticLoader(args.batch_size, max(1, args.steps_per_epoch // 10), model.num_classes, 7 + rank, 'cuda', img)
     model.train()
     for epoch in range(args.epochs):
