@@ -213,6 +213,10 @@ _SIGS = {
     'ga_rand_augment': ([vp, vp, vp, C.c_size_t, i32, i32, i32, i32, vp, i32, vp, vp], i32),
     'ga_rand_augment_work_bytes': ([i32, i32, i32, i32, i32], C.c_size_t),
     'ga_rand_augment_check_table': ([vp, i32], i32),
+    'ga_resize_crop': ([vp, C.c_uint64, vp, vp, vp, C.c_size_t, i32, i32, i32, vp], i32),
+    'ga_resize_crop_work_bytes': ([vp, i32, i32, i32], C.c_size_t),
+    'ga_resize_crop_check_table': ([vp, i32, i32, i32, C.c_uint64], i32),
+    'ga_resample_coeffs': ([i32, i32, i32, vp, vp, i32, vp], i32),
     'ga_mixup_batch': ([vp, vp, i32, i32, i32, i32, C.c_double, i32, i32, i32, i32, i32, vp], i32),
     'ga_mixup_target': ([vp, vp, i32, i32, C.c_double, C.c_double, vp], i32),
     'ga_agc_clip': ([vp, vp, vp, i32, f32, f32, vp], i32),

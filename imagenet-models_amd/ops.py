@@ -804,6 +804,17 @@ class Plan:
     def rand_augment_work_bytes(self, B, CH, H, W, n_layers):
         return int(self.lib.ga_rand_augment_work_bytes(B, CH, H, W, int(n_layers)))
 
+    def resize_crop(self, src, table, out, work, B, OH, OW, label=None):
+        """crop + PIL-exact resize (+ flip, + window) of decoded images: src = device uint8 byte buffer of interleaved HWC images,
+        table = device uint8 (B, 64) of rows {src_off, src_h, src_w, top, left, h, w, vh, vw, oy, ox, interp, flip} (include/gaext.h),
+        out = uint8 (B, 3, OH, OW), work = device uint8 scratch of ga_resize_crop_work_bytes(host table) bytes"""
+        self.record('ga_resize_crop', src, _u64(_nbytes(src)), table, out, work, C.c_size_t(_nbytes(work)), int(B), int(OH), int(OW),
+                    label=label)
+
+    def resample_coeffs(self, in_size, out_size, interp, bounds, coeffs, ksize, label=None):
+        """one axis of PIL's 8-bit resample coefficients: bounds = device int32 (out, 2), coeffs = device int32 (out, ksize)"""
+        self.record('ga_resample_coeffs', int(in_size), int(out_size), int(interp), bounds, coeffs, int(ksize), label=label)
+
     def mixup_target_elem(self, target, out, NC, lam, smoothing, label=None):
         """dense target of per-sample lams: lam = device fp32 (B,)"""
         self.record('ga_mixup_target_elem', target, out, target.numel(), NC, lam, float(smoothing), label=label)

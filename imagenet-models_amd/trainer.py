@@ -11,6 +11,8 @@ which name prefixes it sealed at which mark of its backward plan, and `backward_
 import torch
 import torch.distributed as dist
 
+from .resize_crop import RaggedBatch
+
 _KINDS = {'ce': 0, 'bce': 1}
 
 BUCKET_ELEMS = 8 << 20     # 32 MB of fp32 per all-reduce: enough to run at link rate over xGMI, small enough to pipeline
@@ -66,7 +68,7 @@ class TrainStep:
     def __init__(self, model, optimizer, batch, lam=0.0, loss='ce', smoothing=0.0, grad_accumulation=1,
                  process_group=None, clip_grad=None, clip_mode='norm', broadcast_buffers=True, bucket_elems=BUCKET_ELEMS,
                  mixup_fn=None, bce_target_thresh=None, comm=None, force_buckets=False, nan_guard=False,
-                 overlap_optimizer=False, random_erasing=None, collate_mixup=None, auto_augment=None):
+                 overlap_optimizer=False, random_erasing=None, collate_mixup=None, auto_augment=None, crop=None):
         """The input stage has two orders.
         Default (mixup_fn / random_erasing): normalise -> erase -> mixup -> engine, all in fp32.  random_erasing is an
         imagenet_models_amd.RandomErasing (for a uint8 batch the erase pass IS the normalisation, ga_input_erase, so the batch is
@@ -82,6 +84,9 @@ class TrainStep:
         auto_augment (opt-in): an imagenet_models_amd.RandAugment -- timm's --aa rand-..., which timm applies to the cropped uint8
         image ahead of fast_collate: it runs FIRST, on the uint8 batch (ga_rand_augment), and hands its uint8 result to whichever
         input stage is configured above.  It needs a uint8 batch.
+        crop (opt-in): an imagenet_models_amd.RandomResizedCrop -- the step then takes a RaggedBatch of DECODED images
+        (imagenet_models_amd.pack_images) instead of a tensor: the crop, the resize and the flip run first (ga_resize_crop) and their
+        uint8 batch goes on exactly as a loader's uint8 batch does.
         comm: an imagenet_models_amd.NativeComm -- the gradient buckets (and the BatchNorm-buffer broadcast) go through the
         library's own RCCL entry points (ga_allreduce_bucket on a side stream) instead of torch.distributed.
         force_buckets: take the segmented-backward + bucketed-reduction path even with one rank (tests: the real collective
@@ -101,6 +106,7 @@ class TrainStep:
         self.collate_mixup = collate_mixup
         self.random_erasing = random_erasing
         self.auto_augment = auto_augment
+        self.crop = crop
         self.bce_threshold = -1.0 if bce_target_thresh is None else float(bce_target_thresh)
         self.accum = grad_accumulation
         self.pg = process_group
@@ -194,7 +200,15 @@ class TrainStep:
         main.wait_event(self._opt_done)
         opt.step_end()
 
+    @staticmethod
+    def check_input(x, crop):
+        """a RaggedBatch of decoded images goes with crop=..., a tensor without"""
+        if isinstance(x, RaggedBatch) != (crop is not None):
+            raise TypeError('TrainStep(crop=...) takes a RaggedBatch of decoded images, and a RaggedBatch needs TrainStep(crop=...): '
+                            f'got {type(x).__name__} with crop {"set" if crop is not None else "None"}')
+
     def __call__(self, x, target):
+        self.check_input(x, self.crop)
         eng = self.eng
         self.model.check_flat_generation(self.gen, 'TrainStep')
         last_micro = (self.micro + 1) % self.accum == 0
@@ -208,6 +222,8 @@ class TrainStep:
                 dist.broadcast(self.flat_buffers, 0, group=self.pg)
         # the reference divides the loss by grad_accumulation (train.py:750); DDP averages over ranks
         scale = 1.0 / (self.accum * self.world)
+        if self.crop is not None:
+            x = self.crop(x)
         if self.auto_augment is not None:
             if x.dtype != torch.uint8:
                 raise TypeError(f'TrainStep(auto_augment=...) augments the uint8 batch of the loader, got {x.dtype}')

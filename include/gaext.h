@@ -667,6 +667,54 @@ int ga_rand_augment(const void* x, void* out, void* work, size_t work_bytes, int
                     const uint8_t* fill, ga_stream_t stream);
 size_t ga_rand_augment_work_bytes(int B, int CH, int H, int W, int n_layers);
 int ga_rand_augment_check_table(const void* ops_host, int rows);
+/* The first step of every recipe's input stage, on DECODED images: timm's RandomResizedCropAndInterpolation + RandomHorizontalFlip
+ * (training, GA/train.py:195-217 through create_loader) and Resize(floor(img / crop_pct)) + CenterCrop (evaluation), which timm runs
+ * on the host, per image, with PIL's antialiased resize.  Every output byte equals what PIL gives for the calls timm and torchvision
+ * make: img.crop(box).resize((vw, vh), code), transpose(FLIP_LEFT_RIGHT), the centre window.
+ * src: one DEVICE byte buffer of src_bytes bytes holding RGB images back to back, interleaved HWC as a decoder produces them, row
+ * pitch 3 * src_w bytes without padding (rows are in general not 4-byte aligned).  out: the uint8 NCHW (B, 3, OH, OW) batch of timm's
+ * fast_collate -- what ga_rand_augment, ga_input_collate, ga_input_erase and ga_u8_normalize take; the HWC -> CHW transpose is part
+ * of the pass.  rows: DEVICE table of one 64-byte row per sample, drawn by the host (imagenet_models_amd.RandomResizedCrop /
+ * ResizeCenterCrop):
+ *   { int64 src_off; int32 src_h, src_w;   image b starts at src + src_off
+ *     int32 top, left, h, w;               crop box; the resample sees ONLY the box (crop first, then resize: taps clamp at the box edge)
+ *     int32 vh, vw;                        size the box is resized to
+ *     int32 oy, ox;                        window of that resized image written to out: rows oy..oy+OH-1, columns ox..ox+OW-1
+ *     int32 interp;                        PIL code: 2 bilinear, 3 bicubic
+ *     int32 flip;                          1: mirror left-right after the resize (ahead of the window)
+ *     int32 pad[2]; }
+ * Training: vh, vw = OH, OW and oy = ox = 0.  Evaluation: the box is the whole image, (vh, vw) the short-side-scaled size and
+ * (oy, ox) the centre crop.
+ * The arithmetic is PIL's ImagingResample for 8-bit channels.  Per axis, in = the box extent, out = vw or vh, everything in double,
+ * every operation separately rounded (no FMA), in the order written:
+ *   scale = in / out;  fs = max(scale, 1.0);  support = S * fs, S = 1 bilinear, 2 bicubic;  ss = 1.0 / fs
+ *   output index xx:  center = (xx + 0.5) * scale
+ *                     xmin = max(0, (int)(center - support + 0.5));  xmax = min(in, (int)(center + support + 0.5))
+ *                     tap x in [xmin, xmax):  w_x = f((x - center + 0.5) * ss)
+ *                     ww = the sum of the w_x in ascending x;  w_x = w_x / ww (a true division; skipped if ww == 0)
+ *                     coefficient = (int)(-0.5 + w_x * 2^22) for w_x < 0, (int)(0.5 + w_x * 2^22) otherwise
+ *   f bilinear, t = |t|:  1.0 - t for t < 1, else 0
+ *   f bicubic, a = -0.5:  ((a + 2.0) * t - (a + 3.0)) * t * t + 1 for t < 1;  (((t - 5) * t + 8) * t - 4) * a for t < 2;  else 0
+ *   output byte = clamp((2^21 + sum pixel * coefficient) >> 22, 0, 255), the sum in int32, the shift arithmetic.
+ * The horizontal pass runs first and is rounded to uint8; the vertical pass runs on those bytes.  PIL skips a pass whose size does
+ * not change: its coefficients are exactly one tap of 2^22, so running it gives the same bytes, and it is run.
+ * The coefficients are computed on the device, per output column and row of the window; ga_resample_coeffs writes one axis of them
+ * with the same device function: DEVICE bounds[out_size][2] = (xmin, count) and coeffs[out_size][ksize], zero past count
+ * (ksize >= min(in_size, (int)ceil(support) * 2 + 1), PIL's row pitch).
+ * work: caller-owned, ga_resize_crop_work_bytes(HOST copy of the table, ...) bytes: B + 1 region offsets, then per sample its
+ * coefficients and bounds and the planar [3][h][OW] bytes between the passes.  No tap count is capped, no LDS tile is used, no
+ * allocation, no host synchronisation, no atomics: the result does not depend on the launch shape.
+ * GA_ERR_BAD_ARG, nothing launched -- from ga_resize_crop_check_table, on a HOST copy of the table before it is staged: a box outside
+ * its image or h or w below 1; src_off + 3 * src_h * src_w > src_bytes; a window outside (vh, vw); interp not 2 or 3; flip not 0 or
+ * 1; any extent at or above 32768; OW % 4 != 0 -- and from ga_resize_crop itself: the same limits on B, OH and OW; out, rows or work
+ * off the 16-byte grid; work_bytes below what a table of one-pixel boxes needs.  The kernels clamp nothing and read nothing outside
+ * a box: a table that fails the check must never reach them.  (A workspace smaller than the DEVICE table needs cannot be seen by the
+ * host: the launches then write nothing but the region offsets.) */
+int ga_resize_crop(const void* src, uint64_t src_bytes, const void* rows, void* out, void* work, size_t work_bytes, int B, int OH, int OW,
+                   ga_stream_t stream);
+size_t ga_resize_crop_work_bytes(const void* rows_host, int B, int OH, int OW);
+int ga_resize_crop_check_table(const void* rows_host, int B, int OH, int OW, uint64_t src_bytes);
+int ga_resample_coeffs(int in_size, int out_size, int interp, int32_t* bounds, int32_t* coeffs, int ksize, ga_stream_t stream);
 /* adaptive gradient clipping (timm adaptive_clip_grad, clip_mode 'agc'): units = int64 {offset, length} pairs into the flat fp32
  * parameter / gradient buffers (a row of a >= 2-d parameter or a whole <= 1-d one); per unit
  * g *= max(|p|, eps) * clip_factor / max(|g|, 1e-6) where |g| exceeds max(|p|, eps) * clip_factor */

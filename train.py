@@ -67,7 +67,16 @@ parser.add_argument('--resplit', action='store_true', default=False, help='Do no
 parser.add_argument('--aa', type=str, default=None, metavar='NAME', help='Use AutoAugment policy, timm\'s "rand-m9-mstd0.5-inc1" form '
                     '(RandAugment only; applied on the device to the uint8 batch, ahead of every other input stage). (default: None)')
 parser.add_argument('--train-interpolation', type=str, default='random', help='Training interpolation of the geometric RandAugment ops '
-                    '(random, bilinear, bicubic, nearest; default: "random")')
+                    '(random, bilinear, bicubic, nearest; default: "random") and of the random-resized crop (random, bilinear, bicubic)')
+# random-resized crop + flip on the device (timm create_loader's scale / ratio / hflip); runs on the decoded images of --synthetic-source
+parser.add_argument('--scale', type=float, nargs=2, default=[0.08, 1.0], metavar=('LO', 'HI'), help='Random resize scale '
+                    '(default: 0.08 1.0)')
+parser.add_argument('--ratio', type=float, nargs=2, default=[3. / 4., 4. / 3.], metavar=('LO', 'HI'), help='Random resize aspect '
+                    'ratio (default: 0.75 1.33)')
+parser.add_argument('--hflip', type=float, default=0.5, help='Horizontal flip training aug probability (default: 0.5)')
+parser.add_argument('--synthetic-source', type=str, default=None, metavar='HxW', help='the synthetic loader yields DECODED images '
+                    '(uint8 HWC, heights and widths within [0.5, 1.5] of H and W) and the step starts with the random-resized crop + '
+                    'flip on the device (default: None, the loader yields cropped batches)')
 parser.add_argument('--drop-path', type=float, default=None)
 parser.add_argument('--grad-accumulation', type=int, default=1)
 parser.add_argument('--GA_lam', type=float, default=0)
@@ -98,19 +107,46 @@ parser.add_argument('--output', default='')
 parser.add_argument('--local_rank', default=0, type=int)
 
 
-class SyntheticLoader:
-    """fixed-shape random batches generated on the device (seed = args.seed + rank, like timm random_seed)"""
+def parse_hw(text):
+    """'375x500' -> (375, 500)"""
+    try:
+        h, w = (int(v) for v in text.lower().split('x'))
+    except ValueError:
+        raise SystemExit(f'--synthetic-source {text!r}: HxW, two positive integers')
+    if h < 2 or w < 2 or h * 1.5 >= 32768 or w * 1.5 >= 32768:
+        raise SystemExit(f'--synthetic-source {text!r}: H and W from 2 up to 21844')
+    return h, w
 
-    def __init__(self, batch, steps, num_classes, seed, device, img=224, uint8=False):
+
+def synthetic_ragged(batch, source, seed, device):
+    """B random decoded images in one device buffer: heights and widths drawn once, within [0.5, 1.5] of the nominal size"""
+    from imagenet_models_amd.resize_crop import RaggedBatch, pack_offsets
+    g = torch.Generator().manual_seed(seed)
+    hs = torch.randint(max(1, source[0] // 2), source[0] * 3 // 2 + 1, (batch,), generator=g).tolist()
+    ws = torch.randint(max(1, source[1] // 2), source[1] * 3 // 2 + 1, (batch,), generator=g).tolist()
+    offsets, total = pack_offsets(hs, ws)
+    data = torch.randint(0, 256, (total,), device=device, dtype=torch.uint8, generator=torch.Generator(device=device).manual_seed(seed))
+    return RaggedBatch(data, offsets, hs, ws)
+
+
+class SyntheticLoader:
+    """fixed-shape random batches generated on the device (seed = args.seed + rank, like timm random_seed); with `source` (H, W)
+    one RaggedBatch of decoded images of varying sizes, built once and yielded every step"""
+
+    def __init__(self, batch, steps, num_classes, seed, device, img=224, uint8=False, source=None):
         self.batch, self.steps, self.nc, self.img, self.uint8 = batch, steps, num_classes, img, uint8
         self.g = torch.Generator(device=device).manual_seed(seed)
         self.device = device
+        self.ragged = synthetic_ragged(batch, source, seed, device) if source is not None else None
 
     def __len__(self):
         return self.steps
 
     def __iter__(self):
         for _ in range(self.steps):
+            if self.ragged is not None:
+                yield self.ragged, torch.randint(0, self.nc, (self.batch,), device=self.device, generator=self.g)
+                continue
             if self.uint8:       # the layout of timm's fast_collate: PrefetchLoader / the collate-time mixup take it from here
                 x = torch.randint(0, 256, (self.batch, 3, self.img, self.img), device=self.device, generator=self.g, dtype=torch.uint8)
             else:
@@ -193,6 +229,13 @@ def main():
             RandAugment(args.aa, interpolation=args.train_interpolation)
         except ValueError as e:
             raise SystemExit(f'train.py: --aa / --train-interpolation: {e}')
+    source = parse_hw(args.synthetic_source) if args.synthetic_source else None
+    if source is not None:
+        from imagenet_models_amd.resize_crop import RandomResizedCrop
+        try:
+            RandomResizedCrop(224, scale=args.scale, ratio=args.ratio, interpolation=args.train_interpolation, hflip=args.hflip)
+        except ValueError as e:
+            raise SystemExit(f'train.py: --scale / --ratio / --train-interpolation with --synthetic-source: {e}')
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', str(args.local_rank)))
@@ -257,15 +300,19 @@ def main():
                                          seed=args.seed + rank)
     # RandAugment as timm's create_transform builds it: fill = the rounded dataset mean, the interpolation of the geometric ops
     auto_augment = A.RandAugment(args.aa, interpolation=args.train_interpolation) if args.aa else None
+    img = getattr(model, 'cfg', {}).get('img_size', 224)
+    # the random-resized crop + flip as timm's create_transform builds them, ahead of everything else: only on decoded sources
+    crop = None
+    if source is not None:
+        crop = A.RandomResizedCrop(img, scale=args.scale, ratio=args.ratio, interpolation=args.train_interpolation, hflip=args.hflip)
     step_fn = A.TrainStep(model, opt, args.batch_size, lam=lam, loss='bce' if args.bce_loss else 'ce',
                           smoothing=args.smoothing, grad_accumulation=args.grad_accumulation,
                           clip_grad=args.clip_grad, clip_mode=args.clip_mode, broadcast_buffers=not args.no_ddp_bb,
                           mixup_fn=mixup_fn, bce_target_thresh=args.bce_target_thresh, comm=comm, random_erasing=random_erasing,
-                          collate_mixup=collate_mixup, auto_augment=auto_augment)
+                          collate_mixup=collate_mixup, auto_augment=auto_augment, crop=crop)
     model_ema = A.ModelEma(model, args.model_ema_decay) if args.model_ema else None
-    img = getattr(model, 'cfg', {}).get('img_size', 224)
     loader = SyntheticLoader(args.batch_size, args.steps_per_epoch, model.num_classes, args.seed + rank, 'cuda', img,
-                             uint8=collate_mixup is not None or auto_augment is not None)
+                             uint8=collate_mixup is not None or auto_augment is not None, source=source)
     eval_loader = SyntheticLoader(args.batch_size, max(1, args.steps_per_epoch // 10), model.num_classes, 7 + rank, 'cuda', img)
     model.train()
     for epoch in range(args.epochs):

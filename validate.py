@@ -3,6 +3,7 @@
 top-1/top-5 with bit-exact lowest-index tie-break, on the libgaext HIP kernels.  Synthetic data only.
 
   python validate.py --synthetic --model ga_convnext_tiny_768 -b 256 --batches 10 [--checkpoint x.pth.tar] [--results-file r.json]
+  python validate.py --synthetic --synthetic-source 375x500 --crop-pct 0.875 ...   decoded images: Resize + CenterCrop on the device
 """
 import argparse
 import json
@@ -24,6 +25,12 @@ parser.add_argument('--checkpoint', default='')
 parser.add_argument('--fp32', action='store_true')
 parser.add_argument('--synthetic', action='store_true')
 parser.add_argument('--results-file', default='')
+parser.add_argument('--crop-pct', type=float, default=0.875, help='centre-crop fraction of the evaluation transform: the short side '
+                    'is resized to floor(img / crop_pct) (default: 0.875; used with --synthetic-source)')
+parser.add_argument('--interpolation', type=str, default='bicubic', help='resize interpolation, bilinear or bicubic '
+                    '(default: bicubic; used with --synthetic-source)')
+parser.add_argument('--synthetic-source', type=str, default=None, metavar='HxW', help='evaluate on DECODED synthetic images (uint8 HWC, '
+                    'heights and widths within [0.5, 1.5] of H and W): Resize + CenterCrop and the normalisation run on the device')
 
 
 def main():
@@ -31,17 +38,30 @@ def main():
     if not args.synthetic:
         raise SystemExit('validate.py: only --synthetic data is shipped')
     import imagenet_models_amd as A
+    crop = source = None
+    if args.synthetic_source:
+        from train import parse_hw, synthetic_ragged
+        source = parse_hw(args.synthetic_source)
+        try:
+            crop = A.ResizeCenterCrop(224, args.crop_pct, args.interpolation)
+        except ValueError as e:
+            raise SystemExit(f'validate.py: --crop-pct / --interpolation: {e}')
     model = A.create_model(args.model, num_classes=args.num_classes, checkpoint_path=args.checkpoint,
                            math_mode='fp32' if args.fp32 else 'bf16').cuda().eval()
     g = torch.Generator(device='cuda').manual_seed(0)
     n = c1 = c5 = 0
     with torch.no_grad():
         img = getattr(model, 'cfg', {}).get('img_size', 224)
+        if source is not None:
+            # decoded sources -> Resize + CenterCrop (ga_resize_crop) -> the uint8 batch, which the engine normalises with the model's
+            # input statistics (ga_u8_normalize) as it does a loader's
+            crop = A.ResizeCenterCrop(img, args.crop_pct, args.interpolation)
+            ragged = synthetic_ragged(args.batch_size, source, 0, 'cuda')
         model(torch.randn(args.batch_size, 3, img, img, device='cuda', generator=g))  # warm-up (MAP/validate.py:240)
         torch.cuda.synchronize()
         t0 = time.time()
         for _ in range(args.batches):
-            x = torch.randn(args.batch_size, 3, img, img, device='cuda', generator=g)
+            x = crop(ragged) if source is not None else torch.randn(args.batch_size, 3, img, img, device='cuda', generator=g)
             y = torch.randint(0, model.num_classes, (args.batch_size,), device='cuda', generator=g)
             _, idx = A.heads_topk(model(x), 5)
             a1, a5 = A.accuracy_from_topk(idx, y, (1, 5))
