@@ -217,6 +217,11 @@ _SIGS = {
     'ga_resize_crop_work_bytes': ([vp, i32, i32, i32], C.c_size_t),
     'ga_resize_crop_check_table': ([vp, i32, i32, i32, C.c_uint64], i32),
     'ga_resample_coeffs': ([i32, i32, i32, vp, vp, i32, vp], i32),
+    'ga_jpeg_probe': ([vp, C.c_size_t, vp], i32),
+    'ga_jpeg_entropy_decode': ([vp, C.c_size_t, vp, C.c_size_t, vp], i32),
+    'ga_jpeg_check_table': ([vp, i32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64], i32),
+    'ga_jpeg_work_bytes': ([vp, i32], C.c_size_t),
+    'ga_jpeg_reconstruct': ([vp, i32, vp, vp, vp, vp, vp], i32),
     'ga_mixup_batch': ([vp, vp, i32, i32, i32, i32, C.c_double, i32, i32, i32, i32, i32, vp], i32),
     'ga_mixup_target': ([vp, vp, i32, i32, C.c_double, C.c_double, vp], i32),
     'ga_agc_clip': ([vp, vp, vp, i32, f32, f32, vp], i32),

@@ -815,6 +815,13 @@ class Plan:
         """one axis of PIL's 8-bit resample coefficients: bounds = device int32 (out, 2), coeffs = device int32 (out, ksize)"""
         self.record('ga_resample_coeffs', int(in_size), int(out_size), int(interp), bounds, coeffs, int(ksize), label=label)
 
+    def jpeg_reconstruct(self, table, n_images, coef, qt, work, dst, label=None):
+        """quantised JPEG coefficients -> interleaved HWC RGB images, byte for byte libjpeg-turbo's: table = device uint8 (n, 64) of
+        rows {coef_off, dst_off, work_off, qt_off, width, height, ncomp, hs, vs, mcus_w, mcus_h} (include/gaext.h), coef = device
+        int16, qt = device uint16 (3 x 64 per image), work = device uint8 scratch of ga_jpeg_work_bytes(host table) bytes, dst = the
+        RaggedBatch byte buffer"""
+        self.record('ga_jpeg_reconstruct', table, int(n_images), coef, qt, work, dst, label=label)
+
     def mixup_target_elem(self, target, out, NC, lam, smoothing, label=None):
         """dense target of per-sample lams: lam = device fp32 (B,)"""
         self.record('ga_mixup_target_elem', target, out, target.numel(), NC, lam, float(smoothing), label=label)

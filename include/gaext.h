@@ -715,6 +715,62 @@ int ga_resize_crop(const void* src, uint64_t src_bytes, const void* rows, void* 
 size_t ga_resize_crop_work_bytes(const void* rows_host, int B, int OH, int OW);
 int ga_resize_crop_check_table(const void* rows_host, int B, int OH, int OW, uint64_t src_bytes);
 int ga_resample_coeffs(int in_size, int out_size, int interp, int32_t* bounds, int32_t* coeffs, int ksize, ga_stream_t stream);
+/* Baseline JPEG files into the byte buffer ga_resize_crop reads: the decoder ahead of the input stage.  The entropy stage runs on the
+ * host, per file and thread-safe (csrc/jpeg_host.h: plain C++, no device call, no allocation, no global state); the pixel
+ * reconstruction runs on the device and equals PIL 12.2 / libjpeg-turbo -- Image.open(f).convert('RGB') -- byte for byte.
+ * ga_jpeg_probe and ga_jpeg_entropy_decode return 0 OK, 1 UNSUPPORTED (a valid file of another kind, or no JPEG at all: hand it to
+ * another decoder), 2 CORRUPT; GA_ERR_BAD_ARG for a null pointer.  They never read past bytes + n nor write past coef_capacity.
+ *   OK: SOF0, or SOF1 with 8-bit samples; Huffman coded; ONE interleaved scan (Ss 0, Se 63, Ah = Al = 0) with the components in frame
+ *   order; 1 component sampled 1 x 1, or 3 components that libjpeg takes for YCbCr (a JFIF marker, or an Adobe marker with transform
+ *   1, or neither and ids other than 'R' 'G' 'B') with the luma sampled 1 x 1, 2 x 1 or 2 x 2 and both chroma 1 x 1; DQT of 8 or 16
+ *   bits with entries up to 32767 (libjpeg's multipliers are signed 16-bit words); DRI / RSTn; width and height below 32768.
+ *   UNSUPPORTED: progressive, arithmetic, lossless, 12-bit, 4 components, RGB-coded, any other sampling, several scans, a height of
+ *   0 (DNL), a missing table, larger extents.  CORRUPT: a header that ends early or contradicts itself, a Huffman table with more
+ *   codes than a length holds, and in the scan: the data ends or a marker appears inside a block, a code no symbol has, a run past
+ *   coefficient 63, anything but the expected RSTn at a restart interval.
+ * info[24] (int64): 0 width, 1 height, 2 components, 3 hmax, 4 vmax, 5 the int16 coefficients of the image, 6 restart interval,
+ *   7 MCUs per row, 8 MCU rows; component c: 9 + 4c .. 12 + 4c = h, v, blocks_w, blocks_h over the MCU-padded grid; 21 + c: its start
+ *   in the coefficient buffer.
+ * coef: QUANTISED coefficients, int16, natural (de-zigzagged) order, per component [blocks_h][blocks_w][64], the components back to
+ *   back; qt: 3 x 64 uint16, the table of component c at 64 c, natural order.  Both caller-owned (slices of a pinned staging buffer).
+ * ga_jpeg_reconstruct: DEVICE table of one 64-byte row per image
+ *   { int64 coef_off;  int16 units into coef      int64 dst_off;  bytes into dst      int64 work_off;  bytes into work
+ *     int32 qt_off;    uint16 units into qt       int32 width, height, ncomp;         int32 hs, vs;    the luma sampling
+ *     int32 mcus_w, mcus_h;                       int32 pad[2]; }
+ * dst: the RaggedBatch byte buffer: image i is uint8 [height][width][3] at dst_off (a multiple of 16), rows unpadded; a grey image
+ * writes Y to all three channels; no byte outside the images is written.  work: ga_jpeg_work_bytes(HOST table) bytes, one byte per
+ * coefficient: the components' planes over the MCU-padded grid between the two launches; work_off is the host's (regions back to back).
+ * The arithmetic, all shifts arithmetic, every intermediate of the IDCT 64-bit:
+ *   dequantise   x = coef * qt
+ *   IDCT         jidctint "islow", CONST_BITS 13, PASS1_BITS 2.  One 1-D pass on i0..i7:
+ *                  z1 = (i2 + i6) 4433; t2 = z1 - i6 15137; t3 = z1 + i2 6270; t0 = (i0 + i4) << 13; t1 = (i0 - i4) << 13
+ *                  t10 = t0 + t3; t13 = t0 - t3; t11 = t1 + t2; t12 = t1 - t2
+ *                  a0..a3 = i7, i5, i3, i1; z1 = a0 + a3; z2 = a1 + a2; z3 = a0 + a2; z4 = a1 + a3; z5 = (z3 + z4) 9633
+ *                  a0 *= 2446; a1 *= 16819; a2 *= 25172; a3 *= 12299; z1 *= -7373; z2 *= -20995
+ *                  z3 = z3 (-16069) + z5; z4 = z4 (-3196) + z5; a0 += z1 + z3; a1 += z2 + z4; a2 += z2 + z3; a3 += z1 + z4
+ *                  out 0/7 = t10 +- a3, 1/6 = t11 +- a2, 2/5 = t12 +- a1, 3/4 = t13 +- a0, each (x + (1 << (s - 1))) >> s
+ *                columns first with s = 11, then rows with s = 18, then clamp(x + 128, 0, 255).  (libjpeg indexes a 1024-entry
+ *                table with the low 10 bits instead of clamping, and its SIMD forms saturate earlier: values no 8-bit image
+ *                encodes to.  The clamp is what is built; PIL's bytes are pinned for real files, tests/golden/jpeg_pil.npz.)
+ *   crop         each chroma plane to cw x ch = ceil(width / hs) x ceil(height / vs) before upsampling: neighbours clamp there
+ *   2 x 1        out[2c] = (3 in[c] + in[c-1] + 1) >> 2; out[2c+1] = (3 in[c] + in[c+1] + 2) >> 2; a missing neighbour is in[c]
+ *   2 x 2        cs[c] = 3 row[r][c] + row[r-1 for an even output row, r+1 for an odd one, clamped to the plane][c]
+ *                out[2c] = (3 cs[c] + cs[c-1] + 8) >> 4; out[2c+1] = (3 cs[c] + cs[c+1] + 7) >> 4; a missing neighbour is cs[c]
+ *   cw <= 2      libjpeg takes its replicating upsamplers: out[y][x] = in[y / vs][x / 2]
+ *   colour       cb, cr minus 128: R = Y + ((91881 cr + 32768) >> 16); B = Y + ((116130 cb + 32768) >> 16);
+ *                G = Y + ((-22554 cb - 46802 cr + 32768) >> 16); each clamped to 0 .. 255
+ * No allocation, no host synchronisation, no atomics; the result does not depend on the launch shape.
+ * GA_ERR_BAD_ARG, nothing launched -- from ga_jpeg_check_table on a HOST copy of the table before it is staged: a row that is not one
+ * of the forms above or whose MCU grid is not the one that covers the image; coefficients, tables, planes or image outside their
+ * buffers (coef_count and qt_count in elements) or off the 16-byte grid -- and from ga_jpeg_reconstruct: a null or misaligned pointer,
+ * n_images outside 1 .. 65535.  The kernels clamp nothing: a table that fails the check must never reach them. */
+int ga_jpeg_probe(const uint8_t* bytes, size_t n, int64_t* info);
+int ga_jpeg_entropy_decode(const uint8_t* bytes, size_t n, int16_t* coef, size_t coef_capacity, uint16_t* qt);
+int ga_jpeg_check_table(const void* rows_host, int n_images, uint64_t coef_count, uint64_t qt_count, uint64_t work_bytes,
+                        uint64_t dst_bytes);
+size_t ga_jpeg_work_bytes(const void* rows_host, int n_images);
+int ga_jpeg_reconstruct(const void* table, int n_images, const int16_t* coef, const uint16_t* qt, void* work, void* dst,
+                        ga_stream_t stream);
 /* adaptive gradient clipping (timm adaptive_clip_grad, clip_mode 'agc'): units = int64 {offset, length} pairs into the flat fp32
  * parameter / gradient buffers (a row of a >= 2-d parameter or a whole <= 1-d one); per unit
  * g *= max(|p|, eps) * clip_factor / max(|g|, 1e-6) where |g| exceeds max(|p|, eps) * clip_factor */

@@ -3,11 +3,14 @@
 reference's GA/train.py (argument names, loss, step, logging line), with the hot path on libgaext HIP kernels.
 
 Differences from the reference, all deliberate: bf16 instead of fp16+GradScaler (`--amp`), a
-`--synthetic` loader (the only one shipped: metric runs use synthetic 3x224x224), gradients reduced once per
+`--synthetic` loader (metric runs use synthetic 3x224x224) beside the folder loader, gradients reduced once per
 optimizer step, and `--device cpu` is refused: the product path has no CPU implementation (the CPU baseline is the
 oracle timed by bench.py).
 
   python train.py --synthetic --model ga_convnext_tiny_768 -b 256 --epochs 1 --steps-per-epoch 50 --GA_lam -0.8
+  python train.py /data/imagenet --model map_resnet50 -b 256 -j 8 --aa rand-m9-mstd0.5-inc1 --collate-mixup --reprob 0.25
+      an image folder (DIR/train/<class>/*.jpg, DIR/validation/...): baseline JPEGs are entropy-decoded on -j host threads and
+      rebuilt, cropped, resized and augmented on the device
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train.py --synthetic ...
 """
 import argparse
@@ -25,7 +28,13 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 _logger = logging.getLogger('train')
 
 parser = argparse.ArgumentParser(description='GA ImageNet training (MI355X-native)')
-parser.add_argument('data_dir', nargs='?', default='', help='dataset root (unused with --synthetic)')
+parser.add_argument('data_dir', nargs='?', default='', help='dataset root: an image folder with one directory per class under the '
+                    'split directories (unused with --synthetic)')
+parser.add_argument('--train-split', default='train', metavar='NAME', help='dataset train split: a directory of the root (default: '
+                    'train; the root itself where it has no such directory)')
+parser.add_argument('--val-split', default='validation', metavar='NAME', help='dataset validation split (default: validation)')
+parser.add_argument('-j', '--workers', type=int, default=8, metavar='N', help='host threads of the JPEG entropy stage, at most 16 '
+                    '(default: 8)')
 parser.add_argument('--model', default='ga_convnext_tiny_768')
 parser.add_argument('--num-classes', type=int, default=None)
 parser.add_argument('-b', '--batch-size', type=int, default=128)
@@ -191,6 +200,31 @@ def train_one_epoch(epoch, step_fn, loader, args, world, rank, model_ema=None):
     return OrderedDict([('loss', losses_m.avg)])
 
 
+def split_dir(root, name):
+    """timm's _search_split: root/name where that is a directory, else the root itself"""
+    if not os.path.isdir(root):
+        raise NotADirectoryError(f'{root!r} is not a directory')
+    cand = os.path.join(root, name)
+    return cand if name and os.path.isdir(cand) else root
+
+
+def validate_folder(model, loader, crop, world):
+    """top-1 / top-5 over exactly the real samples of an evaluation FolderLoader (its last batch is padded to the engine's size)"""
+    import imagenet_models_amd as A
+    model.eval()
+    counts = torch.zeros(3, dtype=torch.int64, device='cuda')          # top-1 hits, top-5 hits, samples
+    with torch.no_grad():
+        for ragged, y, real in loader:
+            _, idx = A.heads_topk(model(crop(ragged)), 5)
+            hit = idx[:real].to(torch.int64) == y[:real, None]
+            counts += torch.stack([hit[:, 0].sum(), hit.any(dim=1).sum(), torch.tensor(real, device='cuda')])
+    if world > 1:
+        dist.all_reduce(counts)
+    model.train()
+    c1, c5, n = (int(v) for v in counts.tolist())
+    return OrderedDict([('top1', 100. * c1 / max(n, 1)), ('top5', 100. * c5 / max(n, 1)), ('samples', n)])
+
+
 def validate(model, loader, args, world):
     import imagenet_models_amd as A
     model.eval()
@@ -216,8 +250,9 @@ def main():
     if args.device != 'cuda':
         raise SystemExit('train.py: --device cpu is not available: the product path runs on the libgaext HIP kernels only '
                          '(the CPU baseline is the oracle timed by `bench.py`, kind "port")')
-    if not args.synthetic:
+    if not args.synthetic and not args.data_dir:
         raise SystemExit('train.py: only --synthetic data is shipped (no dataset / network in this environment)')
+    folder = None if args.synthetic else args.data_dir
     if args.mixup_mode == 'half':
         raise SystemExit("train.py: --mixup-mode half returns half of every batch; the engine is planned for the full batch size, so "
                          "it is not built ('batch', 'pair' or 'elem')")
@@ -230,12 +265,19 @@ def main():
         except ValueError as e:
             raise SystemExit(f'train.py: --aa / --train-interpolation: {e}')
     source = parse_hw(args.synthetic_source) if args.synthetic_source else None
-    if source is not None:
+    if source is not None or folder is not None:
         from imagenet_models_amd.resize_crop import RandomResizedCrop
         try:
             RandomResizedCrop(224, scale=args.scale, ratio=args.ratio, interpolation=args.train_interpolation, hflip=args.hflip)
         except ValueError as e:
-            raise SystemExit(f'train.py: --scale / --ratio / --train-interpolation with --synthetic-source: {e}')
+            raise SystemExit(f"train.py: --scale / --ratio / --train-interpolation with {'--synthetic-source' if folder is None else 'an image folder'}: {e}")
+    if folder is not None:
+        from imagenet_models_amd.dataset import ImageFolder
+        try:
+            train_set = ImageFolder(split_dir(folder, args.train_split))
+            val_set = ImageFolder(split_dir(folder, args.val_split))
+        except (OSError, RuntimeError) as e:
+            raise SystemExit(f'train.py: {e}')
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', str(args.local_rank)))
@@ -303,7 +345,7 @@ def main():
     img = getattr(model, 'cfg', {}).get('img_size', 224)
     # the random-resized crop + flip as timm's create_transform builds them, ahead of everything else: only on decoded sources
     crop = None
-    if source is not None:
+    if source is not None or folder is not None:
         crop = A.RandomResizedCrop(img, scale=args.scale, ratio=args.ratio, interpolation=args.train_interpolation, hflip=args.hflip)
     step_fn = A.TrainStep(model, opt, args.batch_size, lam=lam, loss='bce' if args.bce_loss else 'ce',
                           smoothing=args.smoothing, grad_accumulation=args.grad_accumulation,
@@ -311,19 +353,44 @@ def main():
                           mixup_fn=mixup_fn, bce_target_thresh=args.bce_target_thresh, comm=comm, random_erasing=random_erasing,
                           collate_mixup=collate_mixup, auto_augment=auto_augment, crop=crop)
     model_ema = A.ModelEma(model, args.model_ema_decay) if args.model_ema else None
-    loader = SyntheticLoader(args.batch_size, args.steps_per_epoch, model.num_classes, args.seed + rank, 'cuda', img,
-                             uint8=collate_mixup is not None or auto_augment is not None, source=source)
-    eval_loader = SyntheticLoader(args.batch_size, max(1, args.steps_per_epoch // 10), model.num_classes, 7 + rank, 'cuda', img)
+    decoder = eval_crop = None
+    if folder is not None:
+        # the folder: the files' bytes -> JpegDecoder (host entropy stage on -j threads, reconstruction on the device) -> the crop
+        if len(train_set.classes) > model.num_classes:
+            raise SystemExit(f'train.py: {len(train_set.classes)} class directories, the model has {model.num_classes} classes '
+                             '(--num-classes)')
+        decoder = A.JpegDecoder(threads=args.workers)
+        try:
+            loader = A.FolderLoader(train_set, args.batch_size, decoder, train=True, seed=args.seed, rank=rank, world=world)
+        except ValueError as e:
+            raise SystemExit(f'train.py: {e}')
+        eval_loader = A.FolderLoader(val_set, args.batch_size, decoder, train=False, rank=rank, world=world)
+        eval_crop = A.ResizeCenterCrop(img)              # timm's evaluation defaults: crop_pct 0.875, bicubic
+        if rank == 0:
+            _logger.info('Folder %s: %d training images in %d classes, %d validation images; %d decoder threads', folder,
+                         len(train_set), len(train_set.classes), len(val_set), decoder.threads)
+    else:
+        loader = SyntheticLoader(args.batch_size, args.steps_per_epoch, model.num_classes, args.seed + rank, 'cuda', img,
+                                 uint8=collate_mixup is not None or auto_augment is not None, source=source)
+        eval_loader = SyntheticLoader(args.batch_size, max(1, args.steps_per_epoch // 10), model.num_classes, 7 + rank, 'cuda', img)
     model.train()
     for epoch in range(args.epochs):
         if sched is not None:
             sched.step(epoch)
         if (mixup_fn or collate_mixup) is not None and args.mixup_off_epoch and epoch >= args.mixup_off_epoch:
             (mixup_fn or collate_mixup).mixup_enabled = False      # GA/train.py:705-709, MAP/train.py:846-850
+        if folder is not None:
+            loader.set_epoch(epoch)
         train_metrics = train_one_epoch(epoch, step_fn, loader, args, world, rank, model_ema)
         if world > 1 and args.dist_bn in ('broadcast', 'reduce'):
             A.distribute_bn(model, world, args.dist_bn == 'reduce')
-        eval_metrics = validate(model, eval_loader, args, world)
+        if folder is not None:
+            eval_metrics = validate_folder(model, eval_loader, eval_crop, world)
+            if rank == 0:
+                _logger.info('    evaluated %d images; %d of %d files so far went through the PIL fallback', eval_metrics['samples'],
+                             decoder.fallbacks, decoder.decoded)
+        else:
+            eval_metrics = validate(model, eval_loader, args, world)
         if rank == 0:
             _logger.info('*** epoch %d: train loss %.4f  top1 %.3f  top5 %.3f', epoch, train_metrics['loss'],
                          eval_metrics['top1'], eval_metrics['top5'])

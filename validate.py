@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Validation script (timm-style surface of MAP/validate.py / GA/train.py:validate): sums the head logits in fp32,
-top-1/top-5 with bit-exact lowest-index tie-break, on the libgaext HIP kernels.  Synthetic data only.
+top-1/top-5 with bit-exact lowest-index tie-break, on the libgaext HIP kernels.  Synthetic data, or an image folder.
 
   python validate.py --synthetic --model ga_convnext_tiny_768 -b 256 --batches 10 [--checkpoint x.pth.tar] [--results-file r.json]
   python validate.py --synthetic --synthetic-source 375x500 --crop-pct 0.875 ...   decoded images: Resize + CenterCrop on the device
+  python validate.py /data/imagenet --split validation --model map_resnet50 -b 256 -j 8    accuracy over exactly the folder's images
 """
 import argparse
 import json
@@ -24,6 +25,9 @@ parser.add_argument('--num-classes', type=int, default=None)
 parser.add_argument('--checkpoint', default='')
 parser.add_argument('--fp32', action='store_true')
 parser.add_argument('--synthetic', action='store_true')
+parser.add_argument('--split', default='validation', metavar='NAME', help='dataset split: a directory of the root (default: validation; '
+                    'the root itself where it has no such directory)')
+parser.add_argument('-j', '--workers', type=int, default=8, metavar='N', help='host threads of the JPEG entropy stage, at most 16')
 parser.add_argument('--results-file', default='')
 parser.add_argument('--crop-pct', type=float, default=0.875, help='centre-crop fraction of the evaluation transform: the short side '
                     'is resized to floor(img / crop_pct) (default: 0.875; used with --synthetic-source)')
@@ -33,11 +37,50 @@ parser.add_argument('--synthetic-source', type=str, default=None, metavar='HxW',
                     'heights and widths within [0.5, 1.5] of H and W): Resize + CenterCrop and the normalisation run on the device')
 
 
+def validate_folder(args, A):
+    """DIR[/split]/<class>/*: JpegDecoder -> ResizeCenterCrop -> the model, accuracy over exactly the folder's images"""
+    from train import split_dir
+    try:
+        crop = A.ResizeCenterCrop(224, args.crop_pct, args.interpolation)
+        dataset = A.ImageFolder(split_dir(args.data, args.split))
+    except (ValueError, OSError, RuntimeError) as e:
+        raise SystemExit(f'validate.py: {e}')
+    model = A.create_model(args.model, num_classes=args.num_classes, checkpoint_path=args.checkpoint,
+                           math_mode='fp32' if args.fp32 else 'bf16').cuda().eval()
+    if len(dataset.classes) > model.num_classes:
+        raise SystemExit(f'validate.py: {len(dataset.classes)} class directories, the model has {model.num_classes} classes')
+    img = getattr(model, 'cfg', {}).get('img_size', 224)
+    crop = A.ResizeCenterCrop(img, args.crop_pct, args.interpolation)
+    decoder = A.JpegDecoder(threads=args.workers)
+    loader = A.FolderLoader(dataset, args.batch_size, decoder, train=False)
+    counts = torch.zeros(3, dtype=torch.int64, device='cuda')          # top-1 hits, top-5 hits, samples
+    with torch.no_grad():
+        model(torch.zeros(args.batch_size, 3, img, img, device='cuda'))       # warm-up (MAP/validate.py:240)
+        torch.cuda.synchronize()
+        t0 = time.time()
+        for ragged, y, real in loader:
+            _, idx = A.heads_topk(model(crop(ragged)), 5)
+            hit = idx[:real].to(torch.int64) == y[:real, None]
+            counts += torch.stack([hit[:, 0].sum(), hit.any(dim=1).sum(), torch.tensor(real, device='cuda')])
+        torch.cuda.synchronize()
+        dt = time.time() - t0
+    c1, c5, n = (int(v) for v in counts.tolist())
+    res = dict(model=args.model, top1=round(100 * c1 / n, 4), top5=round(100 * c5 / n, 4),
+               param_count=round(sum(p.numel() for p in model.parameters()) / 1e6, 2), img_per_sec=round(n / dt, 1), samples=n,
+               classes=len(dataset.classes), pil_fallbacks=decoder.fallbacks)
+    print(f' * Acc@1 {res["top1"]:.3f} Acc@5 {res["top5"]:.3f}  over {n} images ({res["img_per_sec"]:.1f} img/s)')
+    print('--result\n' + json.dumps(res, indent=4))
+    if args.results_file:
+        json.dump(res, open(args.results_file, 'w'), indent=4)
+
+
 def main():
     args = parser.parse_args()
-    if not args.synthetic:
+    if not args.synthetic and not args.data:
         raise SystemExit('validate.py: only --synthetic data is shipped')
     import imagenet_models_amd as A
+    if not args.synthetic:
+        return validate_folder(args, A)
     crop = source = None
     if args.synthetic_source:
         from train import parse_hw, synthetic_ragged
