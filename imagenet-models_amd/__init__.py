@@ -33,9 +33,10 @@ from .optim import create_optimizer_v2, FusedSGD, FusedAdamW, FusedLamb, CosineL
 from .mixup import FastCollateMixup, Mixup  # noqa: E402,F401
 from .random_erasing import RandomErasing  # noqa: E402,F401
 from .rand_augment import RandAugment  # noqa: E402,F401
-from .resize_crop import RaggedBatch, pack_images, RandomResizedCrop, ResizeCenterCrop  # noqa: E402,F401
+from .resize_crop import RaggedBatch, pack_images, parse_hw, synthetic_ragged, RandomResizedCrop, ResizeCenterCrop  # noqa: E402,F401
 from .jpeg import JpegDecoder  # noqa: E402,F401
-from .dataset import ImageFolder, FolderLoader  # noqa: E402,F401
+from .dataset import ImageFolder, FolderLoader, split_dir, evaluate_folder  # noqa: E402,F401
+from .input_stage import InputStage  # noqa: E402,F401
 from .trainer import TrainStep, distribute_bn, make_buckets  # noqa: E402,F401
 from .comm import NativeComm  # noqa: E402,F401
 from .checkpoint import save_checkpoint, load_checkpoint, ModelEma  # noqa: E402,F401

@@ -5,7 +5,8 @@ TrainStep(crop=RandomResizedCrop(...)) and ResizeCenterCrop take.  No pixel is t
 
 Training: a permutation per epoch from seed + epoch (set_epoch), strided by rank, the ragged tail dropped -- the engines are planned
 for one batch size.  Evaluation: file order, strided by rank, the last batch padded by repeating the last sample; the third element
-of what it yields is the number of real entries.  One producer thread keeps `prefetch` batches ahead of the consumer."""
+of what it yields is the number of real entries.  One producer thread keeps `prefetch` batches ahead of the consumer.
+evaluate_folder is the accuracy loop over such a loader that both scripts run."""
 import os
 import queue
 import re
@@ -14,12 +15,22 @@ import threading
 import numpy as np
 import torch
 
+from .loss import heads_topk
+
 IMG_EXTENSIONS = ('.jpg', '.jpeg', '.png')
 
 
 def natural_key(s):
     """timm.utils.misc.natural_key: digit runs compare as numbers, the rest case-insensitively"""
     return [int(t) if t.isdigit() else t for t in re.split(r'(\d+)', s.lower())]
+
+
+def split_dir(root, name):
+    """timm's _search_split: root/name where that is a directory, else the root itself"""
+    if not os.path.isdir(root):
+        raise NotADirectoryError(f'{root!r} is not a directory')
+    cand = os.path.join(root, name)
+    return cand if name and os.path.isdir(cand) else root
 
 
 class ImageFolder:
@@ -140,3 +151,15 @@ class FolderLoader:
                     q.get_nowait()
                 except queue.Empty:
                     t.join(0.01)
+
+
+def evaluate_folder(model, loader, crop):
+    """an eval-mode model over an evaluation FolderLoader, crop: a ResizeCenterCrop -> int64 device tensor (top-1 hits, top-5 hits,
+    samples) over exactly the real samples (the last batch is padded to the engine's size)"""
+    counts = torch.zeros(3, dtype=torch.int64, device=loader.device)
+    with torch.no_grad():
+        for ragged, y, real in loader:
+            _, idx = heads_topk(model(crop(ragged)), 5)
+            hit = idx[:real].to(torch.int64) == y[:real, None]
+            counts += torch.stack([hit[:, 0].sum(), hit.any(dim=1).sum(), torch.tensor(real, device=loader.device)])
+    return counts

@@ -372,7 +372,7 @@ class EngineBase:
         """(mean, std) of the uint8 normalisation, 0..255 units: the model's input_mean / input_std or the ImageNet ones"""
         return getattr(self.m, 'input_mean', None) or self.U8_MEAN, getattr(self.m, 'input_std', None) or self.U8_STD
 
-    def _normalize_u8(self, x):
+    def normalize_u8(self, x):
         """a uint8 (B, 3, H, W) batch is normalised on the device into an engine-owned fp32 buffer (no host round trip)"""
         if x.dtype != torch.uint8:
             return x
@@ -383,7 +383,7 @@ class EngineBase:
         return out
 
     def set_input(self, x):
-        x = self._normalize_u8(x)
+        x = self.normalize_u8(x)
         assert x.is_cuda and x.dtype == torch.float32 and tuple(x.shape) == (self.B, 3, self.img, self.img), \
             f'input must be a float32 CUDA tensor of shape {(self.B, 3, self.img, self.img)}, got {tuple(x.shape)} {x.dtype}'
         if not x.is_contiguous():

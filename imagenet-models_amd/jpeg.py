@@ -1,6 +1,6 @@
 """JPEG files into the device input stage: the decoder at the seam resize_crop.pack_images() left open.  A baseline JPEG is split where
 the work changes kind: the entropy stage -- markers and Huffman codes, bit-serial, branchy -- runs on the host, one file per call of
-ga_jpeg_entropy_decode on a small thread pool (ctypes releases the GIL), straight into slices of ONE pinned staging buffer; the pixel
+ga_jpeg_entropy_decode on a small thread pool (ctypes releases the GIL), straight into slices of ONE slot of the pinned staging.Ring; the pixel
 reconstruction -- dequantise, IDCT, chroma upsampling, YCbCr -> RGB, regular and wide -- runs on the device in one
 ga_jpeg_reconstruct launch over a 64-byte row per image, into the RaggedBatch byte buffer RandomResizedCrop / ResizeCenterCrop read.
 The result equals PIL's Image.open(f).convert('RGB') byte for byte (tests/golden/jpeg_pil.npz).
@@ -14,8 +14,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import _lib, ops
-from .resize_crop import RaggedBatch, _Staged, pack_offsets
+from . import _lib, ops, staging
+from .resize_crop import RaggedBatch, pack_offsets
 
 OK, UNSUPPORTED, CORRUPT = 0, 1, 2
 MAX_THREADS = 16
@@ -58,7 +58,7 @@ class JpegDecoder:
         self.fallback = fallback
         self.fallbacks = self.decoded = 0
         self._pool = ThreadPoolExecutor(self.threads, thread_name_prefix='jpeg')
-        self._stage, self._work = _Staged(), None
+        self._ring, self._work = staging.Ring(), None
         self.last = None                     # the table of the last call, for logging / tests
 
     def _entropy(self, job):
@@ -124,7 +124,7 @@ class JpegDecoder:
         out = torch.empty(total, dtype=torch.uint8, device=device)
         if dev_n:
             _lib.check(lib.ga_jpeg_check_table(tab.ctypes.data, len(tab), ncoef, 192 * len(tab), work, out.numel()), 'ga_jpeg_check_table')
-        i, host = self._stage.slot(staged)
+        i, host = self._ring.slot(staged)
         h = host.numpy()
         base = host.data_ptr()
         h[:tab.nbytes] = tab.view(np.uint8).reshape(-1)
@@ -139,10 +139,9 @@ class JpegDecoder:
             h[pix_off[k]:pix_off[k] + a.size] = a.reshape(-1)
         dev = torch.empty(staged, dtype=torch.uint8, device=out.device)
         dev.copy_(host[:staged], non_blocking=True)
-        self._stage.sent(i)
+        self._ring.sent(i)
         if dev_n:
-            if self._work is None or self._work.numel() < work or self._work.device != out.device:
-                self._work = torch.empty(work + work // 4, dtype=torch.uint8, device=out.device)      # grows with the largest batch seen
+            self._work = staging.workspace(self._work, work, out.device)      # grows with the largest batch seen
             ops.Plan(eager=True).jpeg_reconstruct(dev[:tab.nbytes], len(tab), dev[coef_at:coef_at + 2 * ncoef].view(torch.int16),
                                                   dev[qt_at:qt_at + 384 * len(tab)].view(torch.int16), self._work, out)
         for k, a in pixels.items():

@@ -16,10 +16,9 @@ is unpinned (as for oracle/mixup_oracle.py)."""
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, staging
 
 KIND_NONE, KIND_MIXUP, KIND_CUTMIX = 0, 1, 2
-_STAGING = 4       # pinned host tables in flight, as random_erasing.py: a table is rewritten only after its copy of 4 calls ago
 
 
 class Mixup:
@@ -79,7 +78,7 @@ class Mixup:
             raise RuntimeError('Mixup runs on the HIP kernels only (no CPU fallback)')
         if not x.is_floating_point():
             raise TypeError(f'Mixup expects a normalised floating-point batch, got {x.dtype}: normalise uint8 input first '
-                            '(TrainStep does; engine._normalize_u8)')
+                            '(TrainStep does; engine.normalize_u8)')
         B, _, H, W = x.shape
         assert B % 2 == 0, 'Batch size should be even when using this'
         lam, use_cutmix = self._params_per_batch()
@@ -115,7 +114,7 @@ class FastCollateMixup(Mixup):
                          num_classes, rng)
         self.mode = mode
         self.last = None                     # the int32 (B, 8) table of the last call, for logging / tests
-        self._key, self._host, self._copied, self._dev, self._out, self._dense, self._calls = None, None, None, None, None, None, 0
+        self._ring, self._dev, self._out, self._dense = staging.Ring(), None, None, None
 
     def _params_per_elem(self, n):
         lam = np.ones(n, dtype=np.float32)
@@ -178,42 +177,18 @@ class FastCollateMixup(Mixup):
         `table[:, 5:7].view(np.float32)` are l and m"""
         return self._draw(B, H, W)[0]
 
-    def _buffers(self, x):
-        B, C, H, W = x.shape
-        key = (tuple(x.shape), x.device, self.num_classes)
-        if self._key != key:
-            self._key = key
-            # one staging block per slot: the (B, 8) table and, behind it, the B lams of the target kernel
-            self._host = [torch.zeros(B * 9, dtype=torch.int32).pin_memory() for _ in range(_STAGING)]
-            self._copied = [None] * _STAGING
-            self._dev = torch.zeros(B * 9, dtype=torch.int32, device=x.device)
-            self._out = torch.empty(B, C, H, W, dtype=torch.float32, device=x.device)
-            self._dense = torch.empty(B, self.num_classes, dtype=torch.float32, device=x.device)
-
     def __call__(self, x, target, random_erasing=None, mean=None, std=None):
         """x: (B, C, H, W) uint8 on the device (mixed in uint8, then normalised with mean / std, 0..255 units) or fp32 (mixed as
         it is); target: (B,) int64; random_erasing: an imagenet_models_amd.RandomErasing whose boxes are filled in the same
         pass, on the mixed image -> (fp32 batch, dense target (B, num_classes)), both in buffers this object owns and reuses"""
-        if not x.is_cuda:
-            raise RuntimeError('FastCollateMixup runs on the HIP kernels only (no CPU fallback)')
-        if x.dtype not in (torch.uint8, torch.float32) or x.dim() != 4:
-            raise TypeError(f'FastCollateMixup expects a uint8 or float32 (B, C, H, W) batch, got {x.dtype} {tuple(x.shape)}')
-        if x.dtype == torch.uint8 and (mean is None or std is None):
-            raise ValueError('FastCollateMixup on a uint8 batch normalises it in the same pass: pass mean / std (0..255 units)')
+        x = staging.check_batch(x, 'FastCollateMixup', stats=(mean, std))
         B, _, H, W = x.shape
-        x = x.contiguous()
-        self._buffers(x)
         tab, lam = self._draw(B, H, W)
-        slot = self._calls % _STAGING
-        if self._copied[slot] is not None:
-            self._copied[slot].synchronize()          # complete long ago in a running loop: no stall
-        host = self._host[slot].numpy()
-        host[:B * 8] = tab.reshape(-1)
-        host[B * 8:] = tab[:, 5]                       # bits(l): the fp32 lam[B] of ga_mixup_target_elem
-        self._dev.copy_(self._host[slot], non_blocking=True)
-        ev = self._copied[slot] or torch.cuda.Event()
-        ev.record()
-        self._copied[slot] = ev
+        # one staging block: the (B, 8) table and, behind it, bits(l) once more: the fp32 lam[B] of ga_mixup_target_elem
+        self._dev = staging.buffer(self._dev, (B * 9,), torch.int32, x.device)
+        self._ring.upload(np.concatenate((tab.reshape(-1), tab[:, 5])), self._dev)
+        self._out = staging.buffer(self._out, x.shape, torch.float32, x.device)
+        self._dense = staging.buffer(self._dense, (B, self.num_classes), torch.float32, x.device)
         p = ops.Plan(eager=True)
         boxes, max_count, mode, seed, offset = random_erasing.stage(x) if random_erasing is not None else (None, 0, 0, 0, 0)
         p.input_collate(x, self._out, self._dev[:B * 8], boxes, max_count, mode, seed, offset, mean, std)
@@ -222,6 +197,5 @@ class FastCollateMixup(Mixup):
             p.mixup_target(target, self._dense, self.num_classes, lam, self.label_smoothing)
         else:
             p.mixup_target_elem(target, self._dense, self.num_classes, self._dev[B * 8:].view(torch.float32), self.label_smoothing)
-        self._calls += 1
         self.last = tab
         return self._out, self._dense

@@ -14,13 +14,12 @@ import re
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, staging
 
 NONE, AUTOCONTRAST, EQUALIZE, INVERT, POSTERIZE, SOLARIZE, SOLARIZE_ADD, COLOR, CONTRAST, BRIGHTNESS, SHARPNESS, AFFINE = range(12)
 NEAREST, BILINEAR, BICUBIC = 0, 2, 3          # PIL's resampling codes
 _INTERP = {'nearest': NEAREST, 'bilinear': BILINEAR, 'bicubic': BICUBIC}
 _LEVEL_DENOM = 10.0
-_STAGING = 4       # pinned host tables in flight: a table is rewritten only after its copy of 4 calls ago has completed
 
 ROW = np.dtype([('kind', '<i4'), ('interp', '<i4'), ('iarg', '<i4'), ('farg', '<f4'), ('m', '<f8', (6,))])      # 64 bytes
 
@@ -91,7 +90,7 @@ class RandAugment:
         self.rng = rng if rng is not None else random             # timm draws from Python's global generator ...
         self.np_rng = np_rng if np_rng is not None else np.random     # ... and the op indices from numpy's
         self.last = None                     # the table of the last call, for logging / tests
-        self._key, self._host, self._copied, self._dev, self._work, self._out, self._calls = None, None, None, None, None, None, 0
+        self._ring, self._dev, self._work, self._out = staging.Ring(), None, None, None
 
     # -- level functions of a magnitude v in [0, mmax] (timm's _LEVEL_DENOM = 10) ----------------------
     def _negate(self, v):
@@ -155,47 +154,27 @@ class RandAugment:
                 self._row(tab[b, l], OPS[int(idx[l])], H, W)
         return tab
 
-    def _buffers(self, x):
-        B, C, H, W = x.shape
-        key = (tuple(x.shape), x.device)
-        if self._key != key:
-            self._key = key
-            nbytes = B * self.num_layers * ROW.itemsize
-            self._host = [torch.zeros(nbytes, dtype=torch.uint8).pin_memory() for _ in range(_STAGING)]
-            self._copied = [None] * _STAGING
-            self._dev = torch.zeros(nbytes, dtype=torch.uint8, device=x.device)
-            work = ops.Plan(eager=True).rand_augment_work_bytes(B, C, H, W, self.num_layers)
-            self._work = torch.empty(work, dtype=torch.uint8, device=x.device)
-            self._out = torch.empty_like(x)
-
     def stage(self, x, table=None):
         """draw the table of one batch (or take `table`), check it on the host and stage it on the device -> device uint8 table"""
         B, _, H, W = x.shape
-        self._buffers(x)
         tab = self.sample(B, H, W) if table is None else np.ascontiguousarray(table, dtype=ROW)
         if tab.shape != (B, self.num_layers):
             raise ValueError(f'RandAugment table of shape {tab.shape}, expected {(B, self.num_layers)}')
         _lib.check(_lib.load().ga_rand_augment_check_table(tab.ctypes.data, tab.size), 'ga_rand_augment_check_table')
-        slot = self._calls % _STAGING
-        if self._copied[slot] is not None:
-            self._copied[slot].synchronize()          # complete long ago in a running loop: no stall
-        self._host[slot].numpy()[:] = tab.reshape(-1).view(np.uint8)
-        self._dev.copy_(self._host[slot], non_blocking=True)
-        ev = self._copied[slot] or torch.cuda.Event()
-        ev.record()
-        self._copied[slot] = ev
-        self._calls += 1
+        self._dev = staging.buffer(self._dev, (tab.nbytes,), torch.uint8, x.device)
+        self._ring.upload(tab, self._dev)
         self.last = tab
         return self._dev
 
     def __call__(self, x, table=None):
         """x: (B, 3, H, W) uint8 on the device -> the augmented uint8 batch, in a buffer this object owns and reuses; x itself is
         not modified.  table: a ROW (B, n) table to apply instead of a drawn one (tests, replay)"""
-        if not x.is_cuda:
-            raise RuntimeError('RandAugment runs on the HIP kernels only (no CPU fallback)')
-        if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[1] != 3:
-            raise TypeError(f'RandAugment expects a uint8 (B, 3, H, W) batch, got {x.dtype} {tuple(x.shape)}')
-        x = x.contiguous()
+        x = staging.check_batch(x, 'RandAugment', dtypes=(torch.uint8,), channels=3)
         dev = self.stage(x, table)
-        ops.Plan(eager=True).rand_augment(x, self._out, self._work, dev, self.num_layers, self.fill)
+        p = ops.Plan(eager=True)
+        out = staging.buffer(self._out, x.shape, torch.uint8, x.device)
+        if out is not self._out:             # another batch shape or device: the scratch follows it
+            work = p.rand_augment_work_bytes(*x.shape, self.num_layers)
+            self._out, self._work = out, torch.empty(work, dtype=torch.uint8, device=x.device)
+        p.rand_augment(x, self._out, self._work, dev, self.num_layers, self.fill)
         return self._out

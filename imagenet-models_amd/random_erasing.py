@@ -10,12 +10,12 @@ the sampler is a restatement of its published algorithm (parity with timm itself
 import math
 import random
 
+import numpy as np
 import torch
 
-from . import ops
+from . import ops, staging
 
 _MODES = {'const': 0, 'rand': 1, 'pixel': 2}
-_STAGING = 4       # pinned host tables in flight: a table is rewritten only after its copy of 4 calls ago has completed
 
 
 class RandomErasing:
@@ -33,7 +33,7 @@ class RandomErasing:
         self.offset = 0                      # Philox offset: one per call, fresh noise every step from one seed
         self.rng = rng if rng is not None else random      # timm draws from Python's global generator
         self.last_boxes = None               # [(sample, top, left, h, w)] of the last call, in drawing order, for logging / tests
-        self._host, self._copied, self._dev, self._out, self._calls = None, None, None, None, 0
+        self._ring, self._dev, self._out = staging.Ring(), None, None
 
     def sample(self, B, H, W):
         """the erase boxes of one batch, drawn as timm draws them: [(sample, top, left, h, w)] in erase order"""
@@ -57,55 +57,29 @@ class RandomErasing:
                         break
         return boxes
 
-    def _buffers(self, x):
-        B, C, H, W = x.shape
-        key = (tuple(x.shape), x.device)
-        if self._host is None or self._key != key:
-            self._key = key
-            self._host = [torch.zeros(B, self.max_count, 4, dtype=torch.int32).pin_memory() for _ in range(_STAGING)]
-            self._copied = [None] * _STAGING
-            self._dev = torch.zeros(B, self.max_count, 4, dtype=torch.int32, device=x.device)
-            self._out = None
-
     def stage(self, x):
         """draw the boxes of one batch and stage their table on the device, for a launch the caller makes (the fused collate
         pass, mixup.FastCollateMixup) -> (device int32 (B, max_count, 4) table, max_count, mode code, seed, offset of THIS call);
         the offset is advanced: one per call, whoever launches"""
         B, _, H, W = x.shape
-        self._buffers(x)
         boxes = self.sample(B, H, W)
-        slot = self._calls % _STAGING
-        if self._copied[slot] is not None:
-            self._copied[slot].synchronize()          # complete long ago in a running loop: no stall
-        host = self._host[slot]
-        host.zero_()
+        tab = np.zeros((B, self.max_count, 4), dtype=np.int32)
         used = [0] * B
-        tab = host.numpy()
         for i, top, left, h, w in boxes:
             tab[i, used[i]] = (top, left, h, w)
             used[i] += 1
-        self._dev.copy_(host, non_blocking=True)
-        ev = self._copied[slot] or torch.cuda.Event()
-        ev.record()
-        self._copied[slot] = ev
+        self._dev = staging.buffer(self._dev, tab.shape, torch.int32, x.device)
+        self._ring.upload(tab, self._dev)
         offset = self.offset
         self.offset += 1
-        self._calls += 1
         self.last_boxes = boxes
         return self._dev, self.max_count, _MODES[self.mode], self.seed, offset
 
     def __call__(self, x, mean=None, std=None):
         """x: (B, C, H, W) uint8 (normalised with mean / std, 0..255 units, in the same pass) or fp32 (copied) on the device
         -> the erased fp32 batch, in a buffer this object owns and reuses; x itself is not modified"""
-        if not x.is_cuda:
-            raise RuntimeError('RandomErasing runs on the HIP kernels only (no CPU fallback)')
-        if x.dtype not in (torch.uint8, torch.float32) or x.dim() != 4:
-            raise TypeError(f'RandomErasing expects a uint8 or float32 (B, C, H, W) batch, got {x.dtype} {tuple(x.shape)}')
-        if x.dtype == torch.uint8 and (mean is None or std is None):
-            raise ValueError('RandomErasing on a uint8 batch normalises it in the same pass: pass mean / std (0..255 units)')
-        x = x.contiguous()
+        x = staging.check_batch(x, 'RandomErasing', stats=(mean, std))
         dev, max_count, mode, seed, offset = self.stage(x)
-        if self._out is None:
-            self._out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        self._out = staging.buffer(self._out, x.shape, torch.float32, x.device)
         ops.Plan(eager=True).input_erase(x, self._out, dev, max_count, mode, seed, offset, mean, std)
         return self._out

@@ -18,11 +18,10 @@ import random
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, staging
 
 BILINEAR, BICUBIC = 2, 3          # PIL's resampling codes
 _INTERP = {'bilinear': BILINEAR, 'bicubic': BICUBIC}
-_STAGING = 4       # pinned host buffers in flight: one is rewritten only after its copy of 4 calls ago has completed
 
 ROW = np.dtype([('src_off', '<i8'), ('src_h', '<i4'), ('src_w', '<i4'), ('top', '<i4'), ('left', '<i4'), ('h', '<i4'), ('w', '<i4'),
                 ('vh', '<i4'), ('vw', '<i4'), ('oy', '<i4'), ('ox', '<i4'), ('interp', '<i4'), ('flip', '<i4'), ('pad', '<i4', (2,))])
@@ -63,30 +62,7 @@ class RaggedBatch:
         return len(self)
 
 
-class _Staged:
-    """four pinned host buffers in rotation, each guarded by the event of its last copy (as the erase boxes and the RandAugment
-    tables are staged)"""
-
-    def __init__(self):
-        self.host, self.copied, self.calls = [None] * _STAGING, [None] * _STAGING, 0
-
-    def slot(self, nbytes):
-        """-> (index, pinned uint8 buffer of at least nbytes) whose previous copy has completed"""
-        i = self.calls % _STAGING
-        self.calls += 1
-        if self.copied[i] is not None:
-            self.copied[i].synchronize()          # complete long ago in a running loop: no stall
-        if self.host[i] is None or self.host[i].numel() < nbytes:
-            self.host[i] = torch.empty(max(nbytes, 1), dtype=torch.uint8).pin_memory()
-        return i, self.host[i]
-
-    def sent(self, i):
-        ev = self.copied[i] or torch.cuda.Event()
-        ev.record()
-        self.copied[i] = ev
-
-
-_PACK = _Staged()
+_PACK = staging.Ring()
 
 
 def pack_offsets(heights, widths):
@@ -94,6 +70,27 @@ def pack_offsets(heights, widths):
     sizes = (3 * np.asarray(heights, dtype=np.int64) * np.asarray(widths, dtype=np.int64) + 15) & ~np.int64(15)
     offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64) if len(sizes) else np.zeros(0, dtype=np.int64)
     return offsets, int(sizes.sum())
+
+
+def parse_hw(text):
+    """'375x500' -> (375, 500): the nominal size of synthetic decoded images (--synthetic-source)"""
+    try:
+        h, w = (int(v) for v in text.lower().split('x'))
+    except ValueError:
+        raise ValueError(f'--synthetic-source {text!r}: HxW, two positive integers') from None
+    if h < 2 or w < 2 or h * 1.5 >= 32768 or w * 1.5 >= 32768:
+        raise ValueError(f'--synthetic-source {text!r}: H and W from 2 up to 21844')
+    return h, w
+
+
+def synthetic_ragged(batch, source, seed, device):
+    """B random decoded images in one device buffer: heights and widths drawn once, within [0.5, 1.5] of the nominal size"""
+    g = torch.Generator().manual_seed(seed)
+    hs = torch.randint(max(1, source[0] // 2), source[0] * 3 // 2 + 1, (batch,), generator=g).tolist()
+    ws = torch.randint(max(1, source[1] // 2), source[1] * 3 // 2 + 1, (batch,), generator=g).tolist()
+    offsets, total = pack_offsets(hs, ws)
+    data = torch.randint(0, 256, (total,), device=device, dtype=torch.uint8, generator=torch.Generator(device=device).manual_seed(seed))
+    return RaggedBatch(data, offsets, hs, ws)
 
 
 def pack_images(images, device='cuda'):
@@ -127,7 +124,7 @@ class _ResizeCrop:
         if self.OH < 1 or self.OW < 1 or self.OW % 4:
             raise ValueError(f'output size {self.OH} x {self.OW}: the width must be a multiple of 4 (ga_resize_crop)')
         self.last = None                     # the table of the last call, for logging / tests
-        self._tab, self._dev, self._out, self._work = _Staged(), None, None, None
+        self._ring, self._dev, self._out, self._work = staging.Ring(), None, None, None
 
     def check(self, table, src_bytes):
         _lib.check(_lib.load().ga_resize_crop_check_table(table.ctypes.data, len(table), self.OH, self.OW, int(src_bytes)),
@@ -144,15 +141,10 @@ class _ResizeCrop:
             raise ValueError(f'table of shape {tab.shape}, expected {(B,)}')
         self.check(tab, ragged.data.numel())
         need = int(_lib.load().ga_resize_crop_work_bytes(tab.ctypes.data, B, self.OH, self.OW))
-        if self._dev is None or self._dev.numel() != B * ROW.itemsize or self._dev.device != dev:
-            self._dev = torch.zeros(B * ROW.itemsize, dtype=torch.uint8, device=dev)
-            self._out = torch.empty(B, 3, self.OH, self.OW, dtype=torch.uint8, device=dev)
-        if self._work is None or self._work.numel() < need or self._work.device != dev:
-            self._work = torch.empty(need + need // 4, dtype=torch.uint8, device=dev)      # grows with the largest boxes seen
-        i, host = self._tab.slot(tab.nbytes)
-        host.numpy()[:tab.nbytes] = tab.view(np.uint8)
-        self._dev.copy_(host[:tab.nbytes], non_blocking=True)
-        self._tab.sent(i)
+        self._dev = staging.buffer(self._dev, (tab.nbytes,), torch.uint8, dev)
+        self._out = staging.buffer(self._out, (B, 3, self.OH, self.OW), torch.uint8, dev)
+        self._work = staging.workspace(self._work, need, dev)          # grows with the largest boxes seen
+        self._ring.upload(tab, self._dev)
         self.last = tab
         ops.Plan(eager=True).resize_crop(ragged.data, self._dev, self._out, self._work, B, self.OH, self.OW)
         return self._out

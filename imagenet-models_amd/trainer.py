@@ -11,7 +11,7 @@ which name prefixes it sealed at which mark of its backward plan, and `backward_
 import torch
 import torch.distributed as dist
 
-from .resize_crop import RaggedBatch
+from .input_stage import InputStage
 
 _KINDS = {'ce': 0, 'bce': 1}
 
@@ -69,24 +69,8 @@ class TrainStep:
                  process_group=None, clip_grad=None, clip_mode='norm', broadcast_buffers=True, bucket_elems=BUCKET_ELEMS,
                  mixup_fn=None, bce_target_thresh=None, comm=None, force_buckets=False, nan_guard=False,
                  overlap_optimizer=False, random_erasing=None, collate_mixup=None, auto_augment=None, crop=None):
-        """The input stage has two orders.
-        Default (mixup_fn / random_erasing): normalise -> erase -> mixup -> engine, all in fp32.  random_erasing is an
-        imagenet_models_amd.RandomErasing (for a uint8 batch the erase pass IS the normalisation, ga_input_erase, so the batch is
-        passed over once), mixup_fn an imagenet_models_amd.Mixup (or a FastCollateMixup, which on an fp32 batch is timm's Mixup in
-        modes 'elem' / 'pair' as well).  This is timm's PrefetchLoader erase followed by the
-        --no-prefetcher mixup_fn (MAP/train.py:614-626,643-646): a combination timm itself never runs -- the erase boxes of both
-        partners are blended into each other and the mixture is never quantised.  It stays the default because every committed
-        number was taken with it.
-        collate_mixup (opt-in): an imagenet_models_amd.FastCollateMixup -- the order every reference recipe runs (prefetcher on,
-        MAP/train.py:383): mixup / cutmix on the uint8 batch at collate time, each blended value rounded back to uint8, then the
-        normalisation, then random_erasing LAST on the mixed image -- one HIP pass (ga_input_collate).  It needs a uint8 batch,
-        takes this step's random_erasing into the fused pass, and excludes mixup_fn.
-        auto_augment (opt-in): an imagenet_models_amd.RandAugment -- timm's --aa rand-..., which timm applies to the cropped uint8
-        image ahead of fast_collate: it runs FIRST, on the uint8 batch (ga_rand_augment), and hands its uint8 result to whichever
-        input stage is configured above.  It needs a uint8 batch.
-        crop (opt-in): an imagenet_models_amd.RandomResizedCrop -- the step then takes a RaggedBatch of DECODED images
-        (imagenet_models_amd.pack_images) instead of a tensor: the crop, the resize and the flip run first (ga_resize_crop) and their
-        uint8 batch goes on exactly as a loader's uint8 batch does.
+        """mixup_fn, random_erasing, collate_mixup, auto_augment, crop: the pieces of the input stage, which input_stage.InputStage
+        runs in its one order ahead of the forward pass (their meaning and the order are described there).
         comm: an imagenet_models_amd.NativeComm -- the gradient buckets (and the BatchNorm-buffer broadcast) go through the
         library's own RCCL entry points (ga_allreduce_bucket on a side stream) instead of torch.distributed.
         force_buckets: take the segmented-backward + bucketed-reduction path even with one rank (tests: the real collective
@@ -94,19 +78,14 @@ class TrainStep:
         nan_guard: the device-side counterpart of MAP/train.py:887-891 (all_gather of the loss + isnan + exit): the loss value
         rides in the LAST gradient bucket's reduction as one extra element; `last_loss_sum` (a device tensor, the sum of the
         ranks' scaled losses) can be inspected by the caller at its logging interval -- no host synchronisation per step."""
-        if mixup_fn is not None and collate_mixup is not None:
-            raise ValueError('TrainStep: mixup_fn (mix the normalised fp32 batch) and collate_mixup (mix the uint8 batch at collate '
-                             'time) are two orders of the same augmentation: pass one of them')
+        self.input_stage = InputStage(crop, auto_augment, collate_mixup, random_erasing, mixup_fn)
         self.model, self.opt = model, optimizer
         self.eng = model.engine(batch, True)
         self.lam, self.kind, self.smoothing = lam, _KINDS[loss], smoothing
-        # mixup / cutmix (imagenet_models_amd.Mixup, GA/train.py:727-728): applied to every batch, the loss then runs on the
-        # dense target it returns (SoftTargetCrossEntropy / BinaryCrossEntropy, train.py:616-621)
-        self.mixup_fn = mixup_fn
-        self.collate_mixup = collate_mixup
-        self.random_erasing = random_erasing
-        self.auto_augment = auto_augment
-        self.crop = crop
+        # with mixup / cutmix (GA/train.py:727-728) the loss runs on the dense target the stage returns (SoftTargetCrossEntropy /
+        # BinaryCrossEntropy, train.py:616-621)
+        self.mixup_fn, self.collate_mixup, self.random_erasing = mixup_fn, collate_mixup, random_erasing
+        self.auto_augment, self.crop = auto_augment, crop
         self.bce_threshold = -1.0 if bce_target_thresh is None else float(bce_target_thresh)
         self.accum = grad_accumulation
         self.pg = process_group
@@ -200,15 +179,7 @@ class TrainStep:
         main.wait_event(self._opt_done)
         opt.step_end()
 
-    @staticmethod
-    def check_input(x, crop):
-        """a RaggedBatch of decoded images goes with crop=..., a tensor without"""
-        if isinstance(x, RaggedBatch) != (crop is not None):
-            raise TypeError('TrainStep(crop=...) takes a RaggedBatch of decoded images, and a RaggedBatch needs TrainStep(crop=...): '
-                            f'got {type(x).__name__} with crop {"set" if crop is not None else "None"}')
-
     def __call__(self, x, target):
-        self.check_input(x, self.crop)
         eng = self.eng
         self.model.check_flat_generation(self.gen, 'TrainStep')
         last_micro = (self.micro + 1) % self.accum == 0
@@ -222,22 +193,7 @@ class TrainStep:
                 dist.broadcast(self.flat_buffers, 0, group=self.pg)
         # the reference divides the loss by grad_accumulation (train.py:750); DDP averages over ranks
         scale = 1.0 / (self.accum * self.world)
-        if self.crop is not None:
-            x = self.crop(x)
-        if self.auto_augment is not None:
-            if x.dtype != torch.uint8:
-                raise TypeError(f'TrainStep(auto_augment=...) augments the uint8 batch of the loader, got {x.dtype}')
-            x = self.auto_augment(x)
-        if self.collate_mixup is not None:
-            if x.dtype != torch.uint8:
-                raise TypeError(f'TrainStep(collate_mixup=...) mixes the uint8 batch of the loader, got {x.dtype}')
-            x, target = self.collate_mixup(x, target, self.random_erasing, *eng.input_stats())
-        elif self.random_erasing is not None:
-            x = self.random_erasing(x, *eng.input_stats())
-        if self.mixup_fn is not None:
-            # a uint8 batch (PrefetchLoader layout) is normalised on the device FIRST: Mixup blends normalised pixels, and a
-            # float tensor coming back from it would make the engine skip the normalisation
-            x, target = self.mixup_fn(eng._normalize_u8(x), target)
+        x, target = self.input_stage(x, target, eng)
         loss = eng.forward_loss(x, target, self.lam, self.kind, self.smoothing, scale, self.bce_threshold)
         if self.overlap_opt and last_micro:
             self._backward_with_updates()

@@ -226,11 +226,11 @@ def test_train_step_input_types():
     assert len(ragged) == 1 and ragged.size(0) == 1
     crop = A.RandomResizedCrop(32)
     with pytest.raises(TypeError, match='RaggedBatch needs TrainStep'):
-        A.TrainStep.check_input(ragged, None)
+        A.InputStage(crop=None).check(ragged)
     with pytest.raises(TypeError, match='takes a RaggedBatch'):
-        A.TrainStep.check_input(torch.zeros(1, 3, 32, 32, dtype=torch.uint8), crop)
-    A.TrainStep.check_input(ragged, crop)
-    A.TrainStep.check_input(torch.zeros(1, 3, 32, 32), None)
+        A.InputStage(crop=crop).check(torch.zeros(1, 3, 32, 32, dtype=torch.uint8))
+    A.InputStage(crop=crop).check(ragged)
+    A.InputStage(crop=None).check(torch.zeros(1, 3, 32, 32))
     with pytest.raises(TypeError, match='takes a RaggedBatch'):
         crop(torch.zeros(1, 3, 32, 32, dtype=torch.uint8))
     with pytest.raises(RuntimeError, match='no CPU fallback'):

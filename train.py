@@ -16,14 +16,18 @@ oracle timed by bench.py).
 import argparse
 import logging
 import os
+import random
 import sys
 import time
 from collections import OrderedDict
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import imagenet_models_amd as A  # noqa: E402
+from imagenet_models_amd import parse_hw, split_dir, synthetic_ragged  # noqa: E402,F401
 
 _logger = logging.getLogger('train')
 
@@ -116,28 +120,6 @@ parser.add_argument('--output', default='')
 parser.add_argument('--local_rank', default=0, type=int)
 
 
-def parse_hw(text):
-    """'375x500' -> (375, 500)"""
-    try:
-        h, w = (int(v) for v in text.lower().split('x'))
-    except ValueError:
-        raise SystemExit(f'--synthetic-source {text!r}: HxW, two positive integers')
-    if h < 2 or w < 2 or h * 1.5 >= 32768 or w * 1.5 >= 32768:
-        raise SystemExit(f'--synthetic-source {text!r}: H and W from 2 up to 21844')
-    return h, w
-
-
-def synthetic_ragged(batch, source, seed, device):
-    """B random decoded images in one device buffer: heights and widths drawn once, within [0.5, 1.5] of the nominal size"""
-    from imagenet_models_amd.resize_crop import RaggedBatch, pack_offsets
-    g = torch.Generator().manual_seed(seed)
-    hs = torch.randint(max(1, source[0] // 2), source[0] * 3 // 2 + 1, (batch,), generator=g).tolist()
-    ws = torch.randint(max(1, source[1] // 2), source[1] * 3 // 2 + 1, (batch,), generator=g).tolist()
-    offsets, total = pack_offsets(hs, ws)
-    data = torch.randint(0, 256, (total,), device=device, dtype=torch.uint8, generator=torch.Generator(device=device).manual_seed(seed))
-    return RaggedBatch(data, offsets, hs, ws)
-
-
 class SyntheticLoader:
     """fixed-shape random batches generated on the device (seed = args.seed + rank, like timm random_seed); with `source` (H, W)
     one RaggedBatch of decoded images of varying sizes, built once and yielded every step"""
@@ -200,24 +182,10 @@ def train_one_epoch(epoch, step_fn, loader, args, world, rank, model_ema=None):
     return OrderedDict([('loss', losses_m.avg)])
 
 
-def split_dir(root, name):
-    """timm's _search_split: root/name where that is a directory, else the root itself"""
-    if not os.path.isdir(root):
-        raise NotADirectoryError(f'{root!r} is not a directory')
-    cand = os.path.join(root, name)
-    return cand if name and os.path.isdir(cand) else root
-
-
 def validate_folder(model, loader, crop, world):
-    """top-1 / top-5 over exactly the real samples of an evaluation FolderLoader (its last batch is padded to the engine's size)"""
-    import imagenet_models_amd as A
+    """top-1 / top-5 over exactly the real samples of an evaluation FolderLoader, summed over the ranks"""
     model.eval()
-    counts = torch.zeros(3, dtype=torch.int64, device='cuda')          # top-1 hits, top-5 hits, samples
-    with torch.no_grad():
-        for ragged, y, real in loader:
-            _, idx = A.heads_topk(model(crop(ragged)), 5)
-            hit = idx[:real].to(torch.int64) == y[:real, None]
-            counts += torch.stack([hit[:, 0].sum(), hit.any(dim=1).sum(), torch.tensor(real, device='cuda')])
+    counts = A.evaluate_folder(model, loader, crop)
     if world > 1:
         dist.all_reduce(counts)
     model.train()
@@ -226,7 +194,6 @@ def validate_folder(model, loader, crop, world):
 
 
 def validate(model, loader, args, world):
-    import imagenet_models_amd as A
     model.eval()
     top1_m, top5_m = AverageMeter(), AverageMeter()
     with torch.no_grad():
@@ -258,29 +225,38 @@ def main():
                          "it is not built ('batch', 'pair' or 'elem')")
     if args.mixup_mode not in ('batch', 'pair', 'elem'):
         raise SystemExit(f"train.py: --mixup-mode {args.mixup_mode!r}: 'batch', 'pair' or 'elem'")
-    if args.aa:
-        from imagenet_models_amd.rand_augment import RandAugment
-        try:
-            RandAugment(args.aa, interpolation=args.train_interpolation)
-        except ValueError as e:
-            raise SystemExit(f'train.py: --aa / --train-interpolation: {e}')
-    source = parse_hw(args.synthetic_source) if args.synthetic_source else None
-    if source is not None or folder is not None:
-        from imagenet_models_amd.resize_crop import RandomResizedCrop
-        try:
-            RandomResizedCrop(224, scale=args.scale, ratio=args.ratio, interpolation=args.train_interpolation, hflip=args.hflip)
-        except ValueError as e:
-            raise SystemExit(f"train.py: --scale / --ratio / --train-interpolation with {'--synthetic-source' if folder is None else 'an image folder'}: {e}")
+    try:
+        source = parse_hw(args.synthetic_source) if args.synthetic_source else None
+    except ValueError as e:
+        raise SystemExit(str(e))
     if folder is not None:
-        from imagenet_models_amd.dataset import ImageFolder
         try:
-            train_set = ImageFolder(split_dir(folder, args.train_split))
-            val_set = ImageFolder(split_dir(folder, args.val_split))
+            train_set = A.ImageFolder(split_dir(folder, args.train_split))
+            val_set = A.ImageFolder(split_dir(folder, args.val_split))
         except (OSError, RuntimeError) as e:
             raise SystemExit(f'train.py: {e}')
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', str(args.local_rank)))
+    torch.manual_seed(args.seed + rank)
+    np.random.seed(args.seed + rank)          # timm random_seed(): mixup draws lam / boxes from numpy's global generator
+    random.seed(args.seed + rank)             # ... and RandomErasing draws its boxes from Python's
+    model = A.create_model(args.model, pretrained=False, num_classes=args.num_classes, drop_path_rate=args.drop_path,
+                           math_mode='fp32' if args.fp32 else 'bf16', gram_fp64=True if args.gram_fp64 else None)
+    img = getattr(model, 'cfg', {}).get('img_size', 224)
+    # the flag-dependent transforms, each built once, on the host: a flag they refuse ends the run before the device is touched
+    # RandAugment as timm's create_transform builds it: fill = the rounded dataset mean, the interpolation of the geometric ops
+    try:
+        auto_augment = A.RandAugment(args.aa, interpolation=args.train_interpolation) if args.aa else None
+    except ValueError as e:
+        raise SystemExit(f'train.py: --aa / --train-interpolation: {e}')
+    # the random-resized crop + flip as timm's create_transform builds them, ahead of everything else: only on decoded sources
+    crop = None
+    if source is not None or folder is not None:
+        try:
+            crop = A.RandomResizedCrop(img, scale=args.scale, ratio=args.ratio, interpolation=args.train_interpolation, hflip=args.hflip)
+        except ValueError as e:
+            raise SystemExit(f"train.py: --scale / --ratio / --train-interpolation with {'--synthetic-source' if folder is None else 'an image folder'}: {e}")
     backend = os.environ.get('GA_DIST_BACKEND', 'nccl')          # gloo: rehearsal with ranks sharing a device
     ndev = max(1, torch.cuda.device_count())
     if local >= ndev:
@@ -294,14 +270,7 @@ def main():
             dist.init_process_group('nccl', init_method='env://', device_id=torch.device('cuda', local))
         else:
             dist.init_process_group(backend, init_method='env://')
-    import random
-    import numpy as np
-    import imagenet_models_amd as A
-    torch.manual_seed(args.seed + rank)
-    np.random.seed(args.seed + rank)          # timm random_seed(): mixup draws lam / boxes from numpy's global generator
-    random.seed(args.seed + rank)             # ... and RandomErasing draws its boxes from Python's
-    model = A.create_model(args.model, pretrained=False, num_classes=args.num_classes, drop_path_rate=args.drop_path,
-                           math_mode='fp32' if args.fp32 else 'bf16', gram_fp64=True if args.gram_fp64 else None).cuda()
+    model = model.cuda()
     if world > 1:
         dist.broadcast(model.flat_state()['params'], 0)
         dist.broadcast(model.flat_state()['buffers'], 0)
@@ -340,13 +309,6 @@ def main():
     if args.reprob > 0.:
         random_erasing = A.RandomErasing(probability=args.reprob, mode=args.remode, max_count=args.recount, num_splits=0,
                                          seed=args.seed + rank)
-    # RandAugment as timm's create_transform builds it: fill = the rounded dataset mean, the interpolation of the geometric ops
-    auto_augment = A.RandAugment(args.aa, interpolation=args.train_interpolation) if args.aa else None
-    img = getattr(model, 'cfg', {}).get('img_size', 224)
-    # the random-resized crop + flip as timm's create_transform builds them, ahead of everything else: only on decoded sources
-    crop = None
-    if source is not None or folder is not None:
-        crop = A.RandomResizedCrop(img, scale=args.scale, ratio=args.ratio, interpolation=args.train_interpolation, hflip=args.hflip)
     step_fn = A.TrainStep(model, opt, args.batch_size, lam=lam, loss='bce' if args.bce_loss else 'ce',
                           smoothing=args.smoothing, grad_accumulation=args.grad_accumulation,
                           clip_grad=args.clip_grad, clip_mode=args.clip_mode, broadcast_buffers=not args.no_ddp_bb,
@@ -371,7 +333,7 @@ def main():
                          len(train_set), len(train_set.classes), len(val_set), decoder.threads)
     else:
         loader = SyntheticLoader(args.batch_size, args.steps_per_epoch, model.num_classes, args.seed + rank, 'cuda', img,
-                                 uint8=collate_mixup is not None or auto_augment is not None, source=source)
+                                 uint8=step_fn.input_stage.takes == 'uint8', source=source)
         eval_loader = SyntheticLoader(args.batch_size, max(1, args.steps_per_epoch // 10), model.num_classes, 7 + rank, 'cuda', img)
     model.train()
     for epoch in range(args.epochs):

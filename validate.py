@@ -37,33 +37,25 @@ parser.add_argument('--synthetic-source', type=str, default=None, metavar='HxW',
                     'heights and widths within [0.5, 1.5] of H and W): Resize + CenterCrop and the normalisation run on the device')
 
 
-def validate_folder(args, A):
+def validate_folder(args, A, model, img):
     """DIR[/split]/<class>/*: JpegDecoder -> ResizeCenterCrop -> the model, accuracy over exactly the folder's images"""
-    from train import split_dir
     try:
-        crop = A.ResizeCenterCrop(224, args.crop_pct, args.interpolation)
-        dataset = A.ImageFolder(split_dir(args.data, args.split))
+        crop = A.ResizeCenterCrop(img, args.crop_pct, args.interpolation)
+        dataset = A.ImageFolder(A.split_dir(args.data, args.split))
     except (ValueError, OSError, RuntimeError) as e:
         raise SystemExit(f'validate.py: {e}')
-    model = A.create_model(args.model, num_classes=args.num_classes, checkpoint_path=args.checkpoint,
-                           math_mode='fp32' if args.fp32 else 'bf16').cuda().eval()
+    model = model.cuda().eval()
     if len(dataset.classes) > model.num_classes:
         raise SystemExit(f'validate.py: {len(dataset.classes)} class directories, the model has {model.num_classes} classes')
-    img = getattr(model, 'cfg', {}).get('img_size', 224)
-    crop = A.ResizeCenterCrop(img, args.crop_pct, args.interpolation)
     decoder = A.JpegDecoder(threads=args.workers)
     loader = A.FolderLoader(dataset, args.batch_size, decoder, train=False)
-    counts = torch.zeros(3, dtype=torch.int64, device='cuda')          # top-1 hits, top-5 hits, samples
     with torch.no_grad():
         model(torch.zeros(args.batch_size, 3, img, img, device='cuda'))       # warm-up (MAP/validate.py:240)
-        torch.cuda.synchronize()
-        t0 = time.time()
-        for ragged, y, real in loader:
-            _, idx = A.heads_topk(model(crop(ragged)), 5)
-            hit = idx[:real].to(torch.int64) == y[:real, None]
-            counts += torch.stack([hit[:, 0].sum(), hit.any(dim=1).sum(), torch.tensor(real, device='cuda')])
-        torch.cuda.synchronize()
-        dt = time.time() - t0
+    torch.cuda.synchronize()
+    t0 = time.time()
+    counts = A.evaluate_folder(model, loader, crop)
+    torch.cuda.synchronize()
+    dt = time.time() - t0
     c1, c5, n = (int(v) for v in counts.tolist())
     res = dict(model=args.model, top1=round(100 * c1 / n, 4), top5=round(100 * c5 / n, 4),
                param_count=round(sum(p.numel() for p in model.parameters()) / 1e6, 2), img_per_sec=round(n / dt, 1), samples=n,
@@ -79,27 +71,30 @@ def main():
     if not args.synthetic and not args.data:
         raise SystemExit('validate.py: only --synthetic data is shipped')
     import imagenet_models_amd as A
+    # the model stays on the host until the crop is built from its input size: a flag the crop refuses ends the run before the device
+    model = A.create_model(args.model, num_classes=args.num_classes, checkpoint_path=args.checkpoint,
+                           math_mode='fp32' if args.fp32 else 'bf16')
+    img = getattr(model, 'cfg', {}).get('img_size', 224)
     if not args.synthetic:
-        return validate_folder(args, A)
+        return validate_folder(args, A, model, img)
     crop = source = None
     if args.synthetic_source:
-        from train import parse_hw, synthetic_ragged
-        source = parse_hw(args.synthetic_source)
+        # decoded sources -> Resize + CenterCrop (ga_resize_crop) -> the uint8 batch, which the engine normalises with the model's
+        # input statistics (ga_u8_normalize) as it does a loader's
         try:
-            crop = A.ResizeCenterCrop(224, args.crop_pct, args.interpolation)
+            source = A.parse_hw(args.synthetic_source)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        try:
+            crop = A.ResizeCenterCrop(img, args.crop_pct, args.interpolation)
         except ValueError as e:
             raise SystemExit(f'validate.py: --crop-pct / --interpolation: {e}')
-    model = A.create_model(args.model, num_classes=args.num_classes, checkpoint_path=args.checkpoint,
-                           math_mode='fp32' if args.fp32 else 'bf16').cuda().eval()
+    model = model.cuda().eval()
     g = torch.Generator(device='cuda').manual_seed(0)
     n = c1 = c5 = 0
     with torch.no_grad():
-        img = getattr(model, 'cfg', {}).get('img_size', 224)
         if source is not None:
-            # decoded sources -> Resize + CenterCrop (ga_resize_crop) -> the uint8 batch, which the engine normalises with the model's
-            # input statistics (ga_u8_normalize) as it does a loader's
-            crop = A.ResizeCenterCrop(img, args.crop_pct, args.interpolation)
-            ragged = synthetic_ragged(args.batch_size, source, 0, 'cuda')
+            ragged = A.synthetic_ragged(args.batch_size, source, 0, 'cuda')
         model(torch.randn(args.batch_size, 3, img, img, device='cuda', generator=g))  # warm-up (MAP/validate.py:240)
         torch.cuda.synchronize()
         t0 = time.time()
