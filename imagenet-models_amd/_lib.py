@@ -144,6 +144,10 @@ _SIGS = {
     'ga_wgrad_workspace': ([C.POINTER(WgradDesc)], C.c_size_t),
     'ga_gemm_form': ([C.POINTER(GemmDesc), C.c_char_p, C.c_size_t], i32),
     'ga_wgrad_form': ([C.POINTER(WgradDesc), C.c_char_p, C.c_size_t], i32),
+    'ga_gemm_fewrows': ([C.POINTER(GemmDesc), vp], i32),
+    'ga_wgrad_fewrows': ([C.POINTER(WgradDesc), vp], i32),
+    'ga_gemm_fewrows_form': ([C.POINTER(GemmDesc), C.c_char_p, C.c_size_t], i32),
+    'ga_wgrad_fewrows_form': ([C.POINTER(WgradDesc), C.c_char_p, C.c_size_t], i32),
     'ga_layernorm_fwd': ([vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp], i32),
     'ga_layernorm_bwd': ([vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp], i32),
     'ga_layernorm_bwd_dp': ([vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, i64, i32, vp], i32),

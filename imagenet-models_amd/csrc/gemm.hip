@@ -2000,17 +2000,21 @@ __global__ __launch_bounds__(256) void tn2_reduce_kernel(const float* __restrict
 
 using namespace gasel;      // the selection: gemm_select.h
 
-// the knob table's values of the knobs the selection reads
-Knobs current_knobs() {
+}  // namespace
+
+// the knob table's values of the knobs the selection reads (declared in gemm_select.h: gemm_fewrows.hip asks too)
+gasel::Knobs gasel::current_knobs() {
     Knobs k;
 #define GA_SEL_KNOB(NAME) k.NAME = GA_KNOB(#NAME, Knobs{}.NAME)
     GA_SEL_KNOB(NT_R3); GA_SEL_KNOB(NT_R3_NEIGH2); GA_SEL_KNOB(NT_R3_CONV3S2); GA_SEL_KNOB(NT_PP); GA_SEL_KNOB(NT_PP_MINK);
     GA_SEL_KNOB(NT_BIG); GA_SEL_KNOB(NT_DMA); GA_SEL_KNOB(NT_DMA2); GA_SEL_KNOB(NT_DMA2_MINK); GA_SEL_KNOB(NT_T256);
     GA_SEL_KNOB(TN2); GA_SEL_KNOB(TN2_PATCH2); GA_SEL_KNOB(TN2_WGS); GA_SEL_KNOB(TN2_PART_MIN);
-    GA_SEL_KNOB(CONV3_DIRECT); GA_SEL_KNOB(CONV0_DIRECT); GA_SEL_KNOB(STEM4_WGRAD_DIRECT);
+    GA_SEL_KNOB(CONV3_DIRECT); GA_SEL_KNOB(CONV0_DIRECT); GA_SEL_KNOB(STEM4_WGRAD_DIRECT); GA_SEL_KNOB(FEWROWS); GA_SEL_KNOB(FEWROWS_MAXM);
 #undef GA_SEL_KNOB
     return k;
 }
+
+namespace {
 
 int lds_error(int bytes) {
     ga_set_error("ga_gemm: cannot reserve %d bytes of LDS", bytes);

@@ -31,7 +31,10 @@ struct Knobs {
         NT_DMA2_MINK = 256, NT_T256 = -1;
     int TN2 = 1, TN2_PATCH2 = 1, TN2_WGS = 0, TN2_PART_MIN = 65536;
     int CONV3_DIRECT = 1, CONV0_DIRECT = 1, STEM4_WGRAD_DIRECT = 1;      // the direct kernels of conv3.hip
+    int FEWROWS = 1, FEWROWS_MAXM = 512;                                 // the few-row forms of gemm_fewrows.hip (their own entry points)
 };
+
+Knobs current_knobs();      // gemm.hip: the knob table's values (the one place that looks knobs up)
 
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 inline uintptr_t addr(const void* p) { return reinterpret_cast<uintptr_t>(p); }
@@ -361,6 +364,54 @@ inline void tn_form_name(const ga_wgrad_desc* d, const TnSel& s, char* buf, size
     if (s.form == TN_TN) snprintf(buf, n, "tn");
     else if (s.form != TN_TN2) snprintf(buf, n, "%s:wgs%d", form[s.form], s.split);
     else snprintf(buf, n, "tn2%s:split%d:%s", d->x_kind == GA_A_PATCH2 ? "p" : "", s.split, s.partials ? "partials" : "atomics");
+}
+
+// ---- the few-row forms (gemm_fewrows.hip): entry points of their own, ga_gemm_fewrows / ga_wgrad_fewrows ----
+// nt_select / tn_select and their answers stay what they are (the recorded corpus pins them); these predicates say which
+// descriptors the new entry points take themselves.  Everything else they forward to ga_gemm / ga_wgrad.
+//
+// Two conditions besides what the kernels can compute: the launch has few rows, and the form ga_gemm / ga_wgrad would choose leaves
+// the chip mostly empty -- fewer of its 128-row (128 x 128) tiles, times batch (and split_m), than half the compute units.  That
+// keeps the per-sample Gram products (M = 196, batch 256: 1024 tiles) and the 96 x 2316 products of the Gram embedding (batch 8: 152
+// and 592 tiles) where they are.
+// The row bound: same-process sweep of M = 64 .. 1024 at N x K = 192 x 768 and 768 x 192 (tools/fewrows_ab.py,
+// profiles/r05_fewrows_sweep.json; MI355X, us per launch, old -> new): NT x1.7 .. 2.3 up to M = 512 (13.5 -> 6.0 at 256 x 192 x 768)
+// and x1.23 at 1024 x 768 x 192 (8.4 -> 6.8, 768 workgroups); TN x1.8 .. 2.2 at every M (12.7 -> 6.0 at M = 256, 32.2 -> 15.0 at 1024).
+// FEWROWS_MAXM (default 512) is the bound -- the last M at which both shapes keep x1.7 -- and a knob so that the sweep can look past it.
+
+inline bool nt_fewrows_wanted(const ga_gemm_desc* d, int num_cus, const Knobs& k) {
+    if (!k.FEWROWS || d->dtype != GA_BF16 || d->a_kind != GA_A_PLAIN || d->c_kind != GA_C_PLAIN || d->a_act != GA_ACT_NONE ||
+        d->relu_after)
+        return false;
+    // epilogues: bias, alpha, c_f32, row scale, residual, column sums; GELU (+ GELU' into C2) only as the fc1 epilogue of the bf16
+    // forms (its logistic GELU); H only as the stored derivative (dgrad2)
+    if (d->act != GA_ACT_NONE ? classify_epilogue(d) != EPI_FC1 : d->C2 != nullptr) return false;
+    if (d->H && !d->h_is_deriv) return false;
+    if (d->colsumsq && !d->colsum) return false;
+    // 8-byte accesses of 4 consecutive bf16 (16-byte of 4 floats) at every batch element
+    if (d->strideC % 4 != 0 || (d->R && d->strideR % 4 != 0) || (d->H && d->strideH % 4 != 0) || (d->bias && (addr(d->bias) & 3)))
+        return false;
+    if (d->M > k.FEWROWS_MAXM || d->batch > 65535) return false;
+    // only what ga_gemm runs on the register-staged body: a launch that a knob forces onto another form stays on that form
+    if (nt_select(d, num_cus, k).form != NT_STAGED) return false;
+    return (long)ceil_div(d->M, 128) * ceil_div(d->N, 32 * nt_tile_width(d->N)) * d->batch < num_cus / 2;
+}
+
+// fewrows32x32:plain | fc1 | fc2 | dg2 | generic (the epilogue class of the descriptor), or none
+inline void nt_fewrows_name(const ga_gemm_desc* d, bool wanted, char* buf, size_t n) {
+    const char* const epi[] = {"generic", "plain", "fc1", "fc2", "dg2"};
+    if (wanted) snprintf(buf, n, "fewrows32x32:%s", epi[classify_epilogue(d) + 1]);
+    else snprintf(buf, n, "none");
+}
+
+// the weight gradient with a short reduction: plain bf16 operands; an output that is stored or accumulated by its one workgroup
+// (split_m > 1 without `accumulate` means atomics into a zeroed dW: the caller's row split is its own business)
+inline bool tn_fewrows_wanted(const ga_wgrad_desc* d, int num_cus, const Knobs& k) {
+    if (!k.FEWROWS || d->dtype != GA_BF16 || d->x_kind != GA_A_PLAIN || d->x_act != GA_ACT_NONE) return false;
+    if (!d->accumulate && d->split_m > 1) return false;
+    if (d->M > k.FEWROWS_MAXM || d->batch > 65535) return false;
+    if (tn_select(d, num_cus, k).form != TN_TN) return false;      // (M < 8192 rules the wide form out; the direct kernels have gathers)
+    return (long)ceil_div(d->N, 128) * ceil_div(d->K, 128) * d->split_m * d->batch < num_cus / 2;
 }
 
 #undef GA_SEL_REQUIRE

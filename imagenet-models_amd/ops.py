@@ -389,7 +389,8 @@ class Plan:
                  colsum=colsum, colsumsq=colsumsq, strideCol=strideCol)
         d.a_H, d.a_W, d.a_C = a_dims
         d.c_H, d.c_W, d.c_C = c_dims
-        self.record('ga_gemm', d, label=label)
+        # the heads' few-row products have kernel forms of their own behind their own entry point (gemm_fewrows.hip); asked once, here
+        self.record('ga_gemm' if gemm_fewrows_form(d) == 'none' else 'ga_gemm_fewrows', d, label=label or 'ga_gemm')
 
     # -- global attention (ViT blocks) ---------------------------------------------------------------
     def attn_desc(self, qkv, out, lse, B, N, H, hd, scale, dtype, ldq=None, ldo=None):
@@ -518,7 +519,7 @@ class Plan:
             def patch(ptr, nbytes, d=d):
                 d.workspace, d.ws_bytes = ptr, nbytes
             self._want_workspace(int(need), patch)
-        self.record('ga_wgrad', d, label=label)
+        self.record('ga_wgrad' if wgrad_fewrows_form(d) == 'none' else 'ga_wgrad_fewrows', d, label=label or 'ga_wgrad')
 
     def weight_prep(self, w, G, Co, Ci, KH, KW, dtype, out=None, ldo=0, outT=None, ldt=0, rs=None, cs=None, flip=False,
                     stem=False, row_perm=None, t_cols=0, label=None):
@@ -940,6 +941,19 @@ def wgrad_form(d):
     buf = C.create_string_buffer(64)
     L.check(L.load().ga_wgrad_form(C.byref(d), buf, 64), 'ga_wgrad_form')
     return buf.value.decode()
+
+
+def gemm_fewrows_form(d):
+    """the few-row form ga_gemm_fewrows runs this GemmDesc on itself (ga_gemm_fewrows_form), 'none' when it forwards the descriptor
+    to ga_gemm -- also for a descriptor the launch will reject: the error is the launch's to raise"""
+    buf = C.create_string_buffer(64)
+    return buf.value.decode() if L.load().ga_gemm_fewrows_form(C.byref(d), buf, 64) == 0 else 'none'
+
+
+def wgrad_fewrows_form(d):
+    """... and ga_wgrad_fewrows for this WgradDesc (ga_wgrad_fewrows_form)"""
+    buf = C.create_string_buffer(64)
+    return buf.value.decode() if L.load().ga_wgrad_fewrows_form(C.byref(d), buf, 64) == 0 else 'none'
 
 
 def cswin_attn_bwd_workspace(d):

@@ -173,6 +173,21 @@ size_t ga_wgrad_workspace(const ga_wgrad_desc* d);
 int ga_gemm_form(const ga_gemm_desc* d, char* buf, size_t n);
 int ga_wgrad_form(const ga_wgrad_desc* d, char* buf, size_t n);
 
+/* Few-row forms (gemm_fewrows.hip): the same products for launches with few rows (M <= 512: the heads' one row per image) that
+ * ga_gemm / ga_wgrad would run on a handful of 128-row tiles -- fewer tiles x batch than half the compute units.  Same descriptors,
+ * same validation, same results up to the fp32 summation order; bf16, plain layouts only.
+ *   ga_gemm_fewrows:  32 x 32 output tile per workgroup, the four waves split K, no LDS staging of the operands.  Takes bias, alpha,
+ *                     c_f32, rowscale, R, colsum / colsumsq, the fc1 epilogue (GELU, C2 with c2_mode 2) and H with h_is_deriv.
+ *   ga_wgrad_fewrows: 64 x 64 output tile per workgroup with the whole reduction inside: no split_m, no atomics between workgroups,
+ *                     so dW and dbias come out bit-identical from run to run.
+ * A descriptor they do not take -- or any descriptor when the knob FEWROWS is 0 -- is forwarded to ga_gemm / ga_wgrad unchanged.
+ * The _form queries work like ga_gemm_form and name what the entry point would do itself: fewrows32x32:<epilogue>,
+ * fewrows_tn64x64, or "none" (forwarded). */
+int ga_gemm_fewrows(const ga_gemm_desc* d, ga_stream_t stream);
+int ga_wgrad_fewrows(const ga_wgrad_desc* d, ga_stream_t stream);
+int ga_gemm_fewrows_form(const ga_gemm_desc* d, char* buf, size_t n);
+int ga_wgrad_fewrows_form(const ga_wgrad_desc* d, char* buf, size_t n);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Weight preparation: fp32 master conv/linear weight [G*Co][Ci][KH][KW]  ->  "effective" copies in `dtype`
  *   out [G][Co][ldo]  with k = (ky,kx,ci)   : out = rs[n] * w * cs[ci]          (B operand of the forward GEMM)
