@@ -123,6 +123,8 @@ _SIGS = {
     'ga_dwconv7_bwd_data2': ([vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp], i32),
     'ga_dwconv7_bwd_weight': ([vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, C.c_size_t, vp], i32),
     'ga_dwconv7_bwd_weight_workspace': ([i32, i32, i32, i32, i32], C.c_size_t),
+    'ga_dwconv7_form': ([i32, i32, i32, i32, i32, i32, i32, C.c_char_p, C.c_size_t], i32),
+    'ga_dwconv7_bwd_weight_form': ([i32, i32, i32, i32, i32, C.c_char_p, C.c_size_t], i32),
     'ga_dwconv3_fwd': ([vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp], i32),
     'ga_dwconv3_bwd_data': ([vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], i32),
     'ga_dwconv3_bwd_weight': ([vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, C.c_size_t, vp], i32),

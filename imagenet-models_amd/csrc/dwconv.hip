@@ -558,7 +558,7 @@ template <int TH, int TW> struct DWF {
 };
 
 template <int TH, int TW>
-__global__ __launch_bounds__((DWF<TH, TW>::NT)) void dwconv7_dot2_kernel(const bf16_t* __restrict__ x,
+__global__ __launch_bounds__((DWF<TH, TW>::NT), 4) void dwconv7_dot2_kernel(const bf16_t* __restrict__ x,
                                                                        const float* __restrict__ w49,
                                                                        const float* __restrict__ bias,
                                                                        const bf16_t* __restrict__ res,
@@ -658,6 +658,7 @@ __global__ __launch_bounds__((DWF<TH, TW>::NT)) void dwconv7_dot2_kernel(const b
             float acc[G::TWP];
 #pragma unroll
             for (int o = 0; o < G::TWP; ++o) acc[o] = bv;
+            const int yy = y0 + oy;
             const unsigned char* xp = xs + lane * G::PLX + oy * G::ROWX;
 #pragma unroll
             for (int ky = 0; ky < 7; ++ky) {
@@ -675,11 +676,29 @@ __global__ __launch_bounds__((DWF<TH, TW>::NT)) void dwconv7_dot2_kernel(const b
                     for (int p = 0; p < 4; ++p)
                         acc[o] = dot2bf((o & 1) ? Q[(o >> 1) + p] : P[(o >> 1) + p], wq[ky][p], acc[o]);
             }
-            // lane's channel, TW pixels -> strip[pixel][channel]; then 16-byte NHWC pieces (+ residual) out
+            // backward-data: the residual joins the fp32 sum, so that the result is rounded to bf16 ONCE (added to the strip's bf16
+            // afterwards it was rounded twice: off by half an ulp of the CONVOLUTION where the residual cancels it).  Its 16-byte
+            // pieces pass through the strip the other way first (LDS operations of one wave execute in order: no barrier); where
+            // nothing is staged the lane adds what the strip held, to an element that is never stored.
+            if (res) {
+                __builtin_amdgcn_sched_barrier(0);              // (the loads stay behind the dot2 loop: its registers are taken)
+#pragma unroll
+                for (int it = 0; it < (TW * 8 + 63) / 64; ++it) {
+                    const int i = lane + it * 64;
+                    const int px = i >> 3, pc = i & 7;
+                    if (i < TW * 8 && pc < ncg && yy < H && x0 + px < W)
+                        *reinterpret_cast<uint4*>(strip + px * 128 + pc * 16) =
+                            *reinterpret_cast<const uint4*>(res + (img + (long)yy * W + x0 + px) * C + c0 + pc * 8);
+                }
+                asm volatile("" ::: "memory");
+#pragma unroll
+                for (int o = 0; o < TW; ++o) acc[o] += bf2f(*reinterpret_cast<const bf16_t*>(strip + o * 128 + ch * 2));
+                asm volatile("" ::: "memory");
+            }
+            // lane's channel, TW pixels -> strip[pixel][channel]; then 16-byte NHWC pieces out
 #pragma unroll
             for (int o = 0; o < TW; ++o)
                 *reinterpret_cast<bf16_t*>(strip + o * 128 + ch * 2) = f2bf(acc[o]);
-            const int yy = y0 + oy;
 #pragma unroll
             for (int it = 0; it < (TW * 8 + 63) / 64; ++it) {
                 const int i = lane + it * 64;
@@ -687,21 +706,14 @@ __global__ __launch_bounds__((DWF<TH, TW>::NT)) void dwconv7_dot2_kernel(const b
                 if (i < TW * 8 && pc < ncg && yy < H && x0 + px < W) {
                     uint4 v = *reinterpret_cast<const uint4*>(strip + px * 128 + pc * 16);
                     const long off = (img + (long)yy * W + x0 + px) * C + c0 + pc * 8;
-                    if (res) {
-                        float a[8], r[8];
+                    *reinterpret_cast<uint4*>(y + off) = v;
+                    if (y2) {   // second output: the stored value times a per-image factor
+                        const float sc = y2scale[img / ((long)H * W)];
+                        float a[8];
                         unpack8(v, a);
-                        load8(res + off, r);
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) a[e] += r[e];
-                        store8(y + off, a);
-                        if (y2) {
-                            const float sc = y2scale[img / ((long)H * W)];
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) a[e] = bf2f(f2bf(a[e])) * sc;
-                            store8(y2 + off, a);
-                        }
-                    } else {
-                        *reinterpret_cast<uint4*>(y + off) = v;
+                        for (int e = 0; e < 8; ++e) a[e] *= sc;
+                        store8(y2 + off, a);
                     }
                 }
             }
@@ -731,6 +743,8 @@ struct DWM {
     static constexpr int LDS = OUT0 + 16 * OROW;                     // 16 rows so that the garbage rows 14, 15 stay inside
     static constexpr int XU = PH * NPX * NCG;                        // 800 staging units
     static constexpr int NXU = (XU + NT - 1) / NT;
+    static constexpr int OU = 14 * 14 * NCG;                         // 784 output pieces of 16 bytes: (row, pixel, 8-channel group)
+    static constexpr int NOU = (OU + NT - 1) / NT;
 };
 
 __global__ __launch_bounds__(512) void dwconv7_mfma_kernel(const bf16_t* __restrict__ x, const float* __restrict__ w49,
@@ -781,6 +795,9 @@ __global__ __launch_bounds__(512) void dwconv7_mfma_kernel(const bf16_t* __restr
 
     // staging units of this thread (tile-invariant): (row, pixel pair, 8-channel group)
     uint4 rxa[G::NXU], rxb[G::NXU];
+    // backward-data: the tile's residual pieces travel with the prefetch into the OUT buffer, where the lane that owns an element
+    // adds it to the fp32 sum before the one rounding to bf16 (added to the buffer's bf16 afterwards it was rounded twice)
+    uint4 rr[G::NOU];
     int xrow[G::NXU], xcol[G::NXU], xsrc[G::NXU], xdst[G::NXU];
 #pragma unroll
     for (int j = 0; j < G::NXU; ++j) {
@@ -810,6 +827,14 @@ __global__ __launch_bounds__(512) void dwconv7_mfma_kernel(const bf16_t* __restr
                 if ((unsigned)(xa + 1) < (unsigned)W) rxb[j] = *reinterpret_cast<const uint4*>(src + C);
             }
         }
+        if (res) {
+#pragma unroll
+            for (int it = 0; it < G::NOU; ++it) {
+                const int id = tid + it * G::NT;
+                const int pc = id & 3, px = (id >> 2) % 14, rw = (id >> 2) / 14;
+                if (id < G::OU && pc < ncg) rr[it] = *reinterpret_cast<const uint4*>(res + base + ((long)rw * W + px) * C + pc * 8);
+            }
+        }
     };
     auto commit = [&]() {
 #pragma unroll
@@ -823,6 +848,14 @@ __global__ __launch_bounds__(512) void dwconv7_mfma_kernel(const bf16_t* __restr
                     *reinterpret_cast<unsigned*>(base + (2 * i) * 4 * G::PLX) = __builtin_amdgcn_perm(wb[i], wa[i], 0x05040100u);
                     *reinterpret_cast<unsigned*>(base + (2 * i + 1) * 4 * G::PLX) = __builtin_amdgcn_perm(wb[i], wa[i], 0x07060302u);
                 }
+            }
+        }
+        if (res) {
+#pragma unroll
+            for (int it = 0; it < G::NOU; ++it) {
+                const int id = tid + it * G::NT;
+                const int pc = id & 3, px = (id >> 2) % 14, rw = (id >> 2) / 14;
+                if (id < G::OU && pc < ncg) *reinterpret_cast<uint4*>(ob + rw * G::OROW + px * 64 + pc * 16) = rr[it];
             }
         }
     };
@@ -848,7 +881,10 @@ __global__ __launch_bounds__(512) void dwconv7_mfma_kernel(const bf16_t* __restr
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int ox = 4 * (lane >> 4) + r;
-                if (ox < 14) *reinterpret_cast<bf16_t*>(ob + n * G::OROW + ox * 64 + chl[q] * 2) = f2bf(acc[r]);
+                if (ox < 14) {                      // (rows 14, 15 and the channels beyond the slice: never stored)
+                    bf16_t* o = reinterpret_cast<bf16_t*>(ob + n * G::OROW + ox * 64 + chl[q] * 2);
+                    *o = f2bf(res ? acc[r] + bf2f(*o) : acc[r]);
+                }
             }
         }
         __syncthreads();
@@ -862,21 +898,14 @@ __global__ __launch_bounds__(512) void dwconv7_mfma_kernel(const bf16_t* __restr
                 const int ty = (int)(tt % tiles_y);
                 const long off = ((tt / tiles_y) * H * W + (long)(ty * 14 + rw) * W + tx * 14 + px) * C + c0 + pc * 8;
                 uint4 v = *reinterpret_cast<const uint4*>(ob + rw * G::OROW + px * 64 + pc * 16);
-                if (res) {
-                    float a[8], rr[8];
+                *reinterpret_cast<uint4*>(y + off) = v;
+                if (y2) {   // second output: the stored value times a per-image factor
+                    const float sc = y2scale[tt / tiles_y];
+                    float a[8];
                     unpack8(v, a);
-                    load8(res + off, rr);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) a[e] += rr[e];
-                    store8(y + off, a);
-                    if (y2) {
-                        const float sc = y2scale[tt / tiles_y];
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) a[e] = bf2f(f2bf(a[e])) * sc;
-                        store8(y2 + off, a);
-                    }
-                } else {
-                    *reinterpret_cast<uint4*>(y + off) = v;
+                    for (int e = 0; e < 8; ++e) a[e] *= sc;
+                    store8(y2 + off, a);
                 }
             }
         }
@@ -1178,24 +1207,42 @@ __global__ __launch_bounds__(256, 2) void dwconv7_rs_kernel(const bf16_t* __rest
     dw_wait_vm<0>();                               // no DMA may still be landing when the LDS is handed to the next workgroup
 }
 
-template <bool RES, bool Y2>
-int launch_dwconv_rs_t(const void* x, const float* w49, const float* bias, const void* res, void* y, int B, int H, int W, int C,
-                       int flip, hipStream_t s, void* y2, const float* y2scale) {
-    using G = DWR<RES, Y2>;
-    auto k = dwconv7_rs_kernel<RES, Y2>;
-    static const bool attr_ok =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS) == hipSuccess;
-    if (!attr_ok) {
-        ga_set_error("dwconv7: cannot reserve %d B of LDS", G::LDS);
-        return GA_ERR_HIP;
-    }
-    const int nstrips = cdiv(W, G::TW);
-    const int wpu = cdiv(nstrips * (C / 2), 64);
-    // rows per segment: a multiple of 7 that divides H -- the longest march (least halo re-reading, fewest wave starts) that
-    // still gives every SIMD its two waves (measured at 256 x 56 x 56 x 96: R = 56 0.101 ms, 28 0.118, 14 0.130)
-    int R = GA_KNOB("DW_RS_ROWS", 0);
+// ------------------------------------------------------------------------------------------------
+// Which form serves a geometry, and on which grid: pure host functions of the geometry, the CU count and the knobs.  The
+// launches below run what they return and ga_dwconv7_form / ga_dwconv7_bwd_weight_form print it (include/gaext.h), so the
+// name a test asserts is the kernel, the grid and the R that ran.
+// ------------------------------------------------------------------------------------------------
+struct DwKnobs {
+    int rs, rs_rows, mfma, xcd8;       // DW_RS, DW_RS_ROWS, DW_MFMA, DW_XCD8
+    int wrs, wrs_rows;                 // DWW_RS, DWW_RS_ROWS
+};
+DwKnobs dw_knobs() {
+    DwKnobs k;
+    k.rs = GA_KNOB("DW_RS", 1);
+    k.rs_rows = GA_KNOB("DW_RS_ROWS", 0);
+    k.mfma = GA_KNOB("DW_MFMA", 1);    // 0: never, 1: heuristic (default), 2: every 14 x 14-tiled launch
+    k.xcd8 = GA_KNOB("DW_XCD8", 1);
+    k.wrs = GA_KNOB("DWW_RS", 1);
+    k.wrs_rows = GA_KNOB("DWW_RS_ROWS", 0);
+    return k;
+}
+
+enum { DW_RS_FORM, DW_MFMA_FORM, DW_DOT2_14, DW_DOT2_7, DW_SCALAR_14, DW_SCALAR_7 };
+struct DwSel {
+    int form;
+    int R, nseg, nstrips, wpu;         // register-sliding form
+    long waves;
+    long ntiles;                       // LDS / MFMA forms: tiles, grid
+    int gx, gy;
+};
+
+// rows per segment of the register-sliding forward: a multiple of 7 that divides H -- the longest march (least halo re-reading,
+// fewest wave starts) that still gives every SIMD its two waves (measured at 256 x 56 x 56 x 96: R = 56 0.101 ms, 28 0.118,
+// 14 0.130)
+inline int dw_rs_rows(int B, int H, int wpu, int num_cus, int rows_knob) {
+    int R = rows_knob;
     if (R <= 0 || R % 7 != 0 || H % R != 0) {
-        const long slots = 8L * ga_num_cus();
+        const long slots = 8L * num_cus;
         R = 7;
         for (int d = 1; d <= H / 7; ++d) {
             if ((H / 7) % d != 0) continue;
@@ -1206,17 +1253,86 @@ int launch_dwconv_rs_t(const void* x, const float* w49, const float* bias, const
             }
         }
     }
-    const int nseg = H / R;
-    const long waves = (long)B * nseg * wpu;
+    return R;
+}
+
+DwSel dw_select(int B, int H, int W, int C, bool bf16, int num_cus, const DwKnobs& k) {
+    DwSel s = {};
+    const bool big = H % 14 == 0 && W % 14 == 0;
+    if (bf16) {
+        // register-sliding form (default): C a multiple of 8, H a multiple of 7, any W, tensors below 2 GiB (32-bit buffer offsets)
+        if (C % 8 == 0 && H % 7 == 0 && (long)B * H * W * C * 2 < (1L << 31) && (long)B * (H / 7) * cdiv(W, 4) * C < (1L << 31) &&
+            k.rs) {
+            s.form = DW_RS_FORM;
+            s.nstrips = cdiv(W, 4);
+            s.wpu = cdiv(s.nstrips * (C / 2), 64);
+            s.R = dw_rs_rows(B, H, s.wpu, num_cus, k.rs_rows);
+            s.nseg = H / s.R;
+            s.waves = (long)B * s.nseg * s.wpu;
+            return s;
+        }
+        if (C % 8 == 0) {
+            const int sl = cdiv(C, 64);
+            s.ntiles = big ? (long)B * (H / 14) * (W / 14) : (long)B * cdiv(H, 7) * cdiv(W, 7);
+            // the MFMA form pays a long prologue (Toeplitz fragments) per workgroup: ahead of the dot2 form only when
+            // a workgroup walks many tiles (56 x 56 maps, also as half batches: 0.169 vs 0.192 ms; 28 x 28 and 14 x 14:
+            // 5-10 % behind)
+            const bool many = H * W >= 56 * 56 && s.ntiles * cdiv(C, 32) >= 16L * num_cus;
+            if (big && (k.mfma == 2 || (k.mfma == 1 && many))) {
+                s.form = DW_MFMA_FORM;
+                s.gy = cdiv(C, 32);
+                // grid.x a multiple of 8: workgroup (x, y) then sits on XCD x % 8 for every slice y, so the 32-channel slices of
+                // one tile (64 of the 128 bytes of every line each) share one L2 instead of fetching the line once per slice
+                s.gx = (int)std::min<long>(s.ntiles, std::max(1, num_cus / s.gy));
+                if (k.xcd8 && s.gx >= 16) s.gx = s.gx / 8 * 8;
+                return s;
+            }
+            s.form = big ? DW_DOT2_14 : DW_DOT2_7;
+            s.gy = sl;
+            s.gx = (int)std::min<long>(s.ntiles, std::max(1, (big ? 2 : 4) * num_cus / sl));
+            return s;
+        }
+    }
+    s.form = big ? DW_SCALAR_14 : DW_SCALAR_7;
+    s.ntiles = big ? (long)B * (H / 14) * (W / 14) : (long)B * cdiv(H, 7) * cdiv(W, 7);
+    s.gy = 1;
+    s.gx = (int)(s.ntiles * cdiv(C, kCSF));       // one workgroup per (tile, slice of 32 channels)
+    return s;
+}
+
+void dw_form_name(const DwSel& s, bool bf16, bool has_res, bool has_y2, char* buf, size_t n) {
+    switch (s.form) {
+        case DW_RS_FORM:
+            snprintf(buf, n, "rs:R%d:seg%d:wpu%d%s%s", s.R, s.nseg, s.wpu, has_res ? "+res" : "", has_y2 ? "+y2" : "");
+            break;
+        case DW_MFMA_FORM: snprintf(buf, n, "mfma:gx%d:tiles%ld", s.gx, s.ntiles); break;
+        case DW_DOT2_14: snprintf(buf, n, "dot2_14x14:gx%d:tiles%ld", s.gx, s.ntiles); break;
+        case DW_DOT2_7: snprintf(buf, n, "dot2_7x7:gx%d:tiles%ld", s.gx, s.ntiles); break;
+        default: snprintf(buf, n, "scalar_%s+%s", s.form == DW_SCALAR_14 ? "14x14" : "7x7", bf16 ? "bf16" : "f32");
+    }
+}
+
+template <bool RES, bool Y2>
+int launch_dwconv_rs_t(const void* x, const float* w49, const float* bias, const void* res, void* y, int B, int H, int W, int C,
+                       int flip, hipStream_t s, void* y2, const float* y2scale, const DwSel& sel) {
+    using G = DWR<RES, Y2>;
+    auto k = dwconv7_rs_kernel<RES, Y2>;
+    static const bool attr_ok =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS) == hipSuccess;
+    if (!attr_ok) {
+        ga_set_error("dwconv7: cannot reserve %d B of LDS", G::LDS);
+        return GA_ERR_HIP;
+    }
+    static_assert(G::TW == 4, "dw_select counts strips of 4 columns");
     const unsigned bytes = (unsigned)((long)B * H * W * C * 2);
-    hipLaunchKernelGGL(k, dim3((unsigned)cdiv(waves, 4L)), dim3(256), G::LDS, s, (const bf16_t*)x, w49, bias, (const bf16_t*)res,
-                       (bf16_t*)y, H, W, C, flip, (bf16_t*)y2, y2scale, R, nseg, nstrips, wpu, (int)waves, bytes);
+    hipLaunchKernelGGL(k, dim3((unsigned)cdiv(sel.waves, 4L)), dim3(256), G::LDS, s, (const bf16_t*)x, w49, bias, (const bf16_t*)res,
+                       (bf16_t*)y, H, W, C, flip, (bf16_t*)y2, y2scale, sel.R, sel.nseg, sel.nstrips, sel.wpu, (int)sel.waves, bytes);
     return ga_check_launch("ga_dwconv7");
 }
 
 int launch_dwconv_rs(const void* x, const float* w49, const float* bias, const void* res, void* y, int B, int H, int W, int C,
-                     int flip, hipStream_t s, void* y2, const float* y2scale) {
-#define DW_RS_GO(RES, Y2) return launch_dwconv_rs_t<RES, Y2>(x, w49, bias, res, y, B, H, W, C, flip, s, y2, y2scale)
+                     int flip, hipStream_t s, void* y2, const float* y2scale, const DwSel& sel) {
+#define DW_RS_GO(RES, Y2) return launch_dwconv_rs_t<RES, Y2>(x, w49, bias, res, y, B, H, W, C, flip, s, y2, y2scale, sel)
     const bool r = res != nullptr, t = y2 != nullptr;
     if (r && t) DW_RS_GO(true, true);
     if (r) DW_RS_GO(true, false);
@@ -1441,13 +1557,13 @@ __global__ __launch_bounds__(1024) void dwconv7_wgrad_rs_reduce(const float* __r
 }
 
 // geometry of the register-sliding backward-weight form: rows per segment, workgroups (a multiple of wpu), or 0 if it does not apply
-inline bool dww_rs_geometry(int B, int H, int W, int C, int* R_out, int* wpu_out, int* nb_out) {
+inline bool dww_rs_geometry(int B, int H, int W, int C, int num_cus, int rows_knob, int* R_out, int* wpu_out, int* nb_out) {
     if (C % 8 != 0 || H % 7 != 0 || (long)B * H * W * C * 2 >= (1L << 31)) return false;
     const int nstrips = cdiv(W, DWW::TW);
     const int wpu = cdiv(nstrips * (C / 2), 64);
-    const int nbw = std::max(1, 2 * ga_num_cus() / wpu);          // two workgroups per CU
+    const int nbw = std::max(1, 2 * num_cus / wpu);               // two workgroups per CU
     // rows per segment: the longest march that still gives each of the 4 * nbw waves of a lane map about two units
-    int R = GA_KNOB("DWW_RS_ROWS", 0);
+    int R = rows_knob;
     if (R <= 0 || R % 7 != 0 || H % R != 0) {
         R = 7;
         for (int d = 1; d <= H / 7; ++d) {
@@ -1465,10 +1581,56 @@ inline bool dww_rs_geometry(int B, int H, int W, int C, int* R_out, int* wpu_out
     return true;
 }
 
+// which backward-weight form serves a geometry, its grid and the workspace the launch asks for (see dw_select)
+enum { DWW_RS_FORM, DWW_DOT2_14, DWW_DOT2_7, DWW_SCALAR_14, DWW_SCALAR_7 };
+struct DwwSel {
+    int form;
+    int R, wpu, nb;                    // register-sliding form: rows per segment, waves per unit, workgroups (nbw * wpu)
+    int gx, slices, nparts;            // LDS forms: grid and partials the reduce adds
+    size_t ws_bytes;
+};
+
+DwwSel dww_select(int B, int H, int W, int C, bool bf16, int num_cus, const DwKnobs& k) {
+    DwwSel s = {};
+    s.slices = cdiv(C, kCSW);
+    const bool big = H % 14 == 0 && W % 14 == 0;
+    const long ntiles = big ? (long)B * (H / 14) * (W / 14) : (long)B * cdiv(H, 7) * cdiv(W, 7);
+    const bool dot2 = bf16 && C % 8 == 0;   // dot2 form: 89 KB of LDS at 14x14 -> one workgroup per CU
+    s.gx = (int)std::min<long>(ntiles, std::max(1, (big ? (dot2 ? 1 : 2) : 4) * num_cus / s.slices));
+    const int nparts = s.gx * (big ? 2 : 1);   // one partial per (workgroup, group of 7 output rows)
+    // bytes of partial sums: the larger of the forms that may serve the geometry, whatever the knobs say
+    s.ws_bytes = (size_t)nparts * 50 * C * sizeof(float);
+    const bool rs_ok = bf16 && dww_rs_geometry(B, H, W, C, num_cus, k.wrs_rows, &s.R, &s.wpu, &s.nb);
+    if (rs_ok) s.ws_bytes = std::max(s.ws_bytes, (size_t)s.nb * DWW::NV * 64 * sizeof(float));
+    // register-sliding form: 0 never, 1 (default) on 28 x 28 maps and larger (256 x 56 x 56 x 96: 0.134 vs 0.182 ms, 28 x 28 x 192:
+    // 0.071 vs 0.078; on the smaller maps its per-unit start-up and the 13 MB of partials eat the gain: 14 x 14 0.047 vs 0.044),
+    // 2 wherever it applies
+    if (rs_ok && k.wrs && (k.wrs == 2 || H * W >= 28 * 28)) {
+        s.form = DWW_RS_FORM;
+        s.nparts = s.nb;
+    } else if (dot2) {
+        s.form = big ? DWW_DOT2_14 : DWW_DOT2_7;
+        s.nparts = s.gx;                       // the row groups of a workgroup meet in LDS: one partial each
+    } else {
+        s.form = big ? DWW_SCALAR_14 : DWW_SCALAR_7;
+        s.nparts = nparts;
+    }
+    return s;
+}
+
+void dww_form_name(const DwwSel& s, int H, bool bf16, char* buf, size_t n) {
+    switch (s.form) {
+        case DWW_RS_FORM: snprintf(buf, n, "rs:R%d:seg%d:wpu%d:nbw%d", s.R, H / s.R, s.wpu, s.nb / s.wpu); break;
+        case DWW_DOT2_14: snprintf(buf, n, "dot2_14x14:parts%d", s.nparts); break;
+        case DWW_DOT2_7: snprintf(buf, n, "dot2_7x7:parts%d", s.nparts); break;
+        default:
+            snprintf(buf, n, "scalar_%s:parts%d+%s", s.form == DWW_SCALAR_14 ? "14x14" : "7x7", s.nparts, bf16 ? "bf16" : "f32");
+    }
+}
+
 int launch_dwconv_wgrad_rs(const void* dy, const void* x, float* dw49, float* dbias, int B, int H, int W, int C, float* part,
-                           hipStream_t s) {
-    int R, wpu, nb;
-    dww_rs_geometry(B, H, W, C, &R, &wpu, &nb);
+                           hipStream_t s, const DwwSel& sel) {
+    const int R = sel.R, wpu = sel.wpu, nb = sel.nb;
     static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(dwconv7_wgrad_rs_kernel),
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, DWW::LDS) == hipSuccess;
     if (!attr_ok) {
@@ -1487,12 +1649,10 @@ int launch_dwconv_wgrad_rs(const void* dy, const void* x, float* dw49, float* db
 template <typename T>
 int launch_dwconv(const void* x, const float* w49, const float* bias, const void* res, void* y, int B, int H, int W,
                   int C, int flip, hipStream_t s, void* y2 = nullptr, const float* y2scale = nullptr) {
+    const DwSel sel = dw_select(B, H, W, C, sizeof(T) == 2, ga_num_cus(), dw_knobs());
     if constexpr (sizeof(T) == 2) {
-        // register-sliding form (default): C a multiple of 8, H a multiple of 7, any W, tensors below 2 GiB (32-bit buffer offsets)
-        if (C % 8 == 0 && H % 7 == 0 && (long)B * H * W * C * 2 < (1L << 31) && (long)B * (H / 7) * cdiv(W, 4) * C < (1L << 31) &&
-            GA_KNOB("DW_RS", 1))
-            return launch_dwconv_rs(x, w49, bias, res, y, B, H, W, C, flip, s, y2, y2scale);
-        if (C % 8 == 0) {
+        if (sel.form == DW_RS_FORM) return launch_dwconv_rs(x, w49, bias, res, y, B, H, W, C, flip, s, y2, y2scale, sel);
+        if (sel.form == DW_MFMA_FORM || sel.form == DW_DOT2_14 || sel.form == DW_DOT2_7) {
             using G14 = DWF<14, 14>;
             using G7 = DWF<7, 7>;
             auto k14 = dwconv7_dot2_kernel<14, 14>;
@@ -1505,35 +1665,21 @@ int launch_dwconv(const void* x, const float* w49, const float* bias, const void
                 ga_set_error("dwconv7: cannot reserve %d B of LDS", lds14);
                 return GA_ERR_HIP;
             }
-            const int sl = cdiv(C, 64);
-            const bool big = H % 14 == 0 && W % 14 == 0;
-            const long ntiles = big ? (long)B * (H / 14) * (W / 14) : (long)B * cdiv(H, 7) * cdiv(W, 7);
-            const int gx = (int)std::min<long>(ntiles, std::max(1, (big ? 2 : 4) * ga_num_cus() / sl));
-            const int use_mfma = GA_KNOB("DW_MFMA", 1);     // 0: never, 1: heuristic (default), 2: every 14 x 14-tiled launch
-            // the MFMA form pays a long prologue (Toeplitz fragments) per workgroup: ahead of the dot2 form only when
-            // a workgroup walks many tiles (56 x 56 maps, also as half batches: 0.169 vs 0.192 ms; 28 x 28 and 14 x 14:
-            // 5-10 % behind)
-            const bool many = H * W >= 56 * 56 && ntiles * cdiv(C, DWM::CS) >= 16L * ga_num_cus();
-            if (big && (use_mfma == 2 || (use_mfma == 1 && many))) {
-                const int slm = cdiv(C, DWM::CS);
-                // grid.x a multiple of 8: workgroup (x, y) then sits on XCD x % 8 for every slice y, so the 32-channel slices of
-                // one tile (64 of the 128 bytes of every line each) share one L2 instead of fetching the line once per slice
-                const int xcd8 = GA_KNOB("DW_XCD8", 1);
-                int gxm = (int)std::min<long>(ntiles, std::max(1, ga_num_cus() / slm));
-                if (xcd8 && gxm >= 16) gxm = gxm / 8 * 8;
-                hipLaunchKernelGGL(dwconv7_mfma_kernel, dim3(gxm, slm), dim3(DWM::NT), DWM::LDS, s, (const bf16_t*)x, w49, bias,
+            static_assert(DWM::CS == 32, "dw_select slices the MFMA form by 32 channels");
+            const dim3 grid(sel.gx, sel.gy);
+            if (sel.form == DW_MFMA_FORM)
+                hipLaunchKernelGGL(dwconv7_mfma_kernel, grid, dim3(DWM::NT), DWM::LDS, s, (const bf16_t*)x, w49, bias,
                                    (const bf16_t*)res, (bf16_t*)y, B, H, W, C, flip, (bf16_t*)y2, y2scale);
-            } else if (big)
-                hipLaunchKernelGGL(k14, dim3(gx, sl), dim3(G14::NT), G14::LDS, s, (const bf16_t*)x, w49, bias,
+            else if (sel.form == DW_DOT2_14)
+                hipLaunchKernelGGL(k14, grid, dim3(G14::NT), G14::LDS, s, (const bf16_t*)x, w49, bias,
                                    (const bf16_t*)res, (bf16_t*)y, B, H, W, C, flip, (bf16_t*)y2, y2scale);
             else
-                hipLaunchKernelGGL(k7, dim3(gx, sl), dim3(G7::NT), G7::LDS, s, (const bf16_t*)x, w49, bias,
+                hipLaunchKernelGGL(k7, grid, dim3(G7::NT), G7::LDS, s, (const bf16_t*)x, w49, bias,
                                    (const bf16_t*)res, (bf16_t*)y, B, H, W, C, flip, (bf16_t*)y2, y2scale);
             return ga_check_launch("ga_dwconv7");
         }
     }
-    const int slices = cdiv(C, kCSF);
-    if (H % 14 == 0 && W % 14 == 0) {
+    if (sel.form == DW_SCALAR_14) {
         constexpr int TH = 14, TW = 14, NT = 256;
         const size_t lds = (TH + 6) * (TW + 6) * kCSF * sizeof(T) + 49 * kCSF * 4;
         auto k = dwconv7_kernel<T, TH, TW, NT>;
@@ -1546,61 +1692,33 @@ int launch_dwconv(const void* x, const float* w49, const float* bias, const void
             }
             once = true;
         }
-        dim3 grid(B * (H / TH) * (W / TW) * slices);
+        dim3 grid(sel.gx);
         hipLaunchKernelGGL(k, grid, dim3(NT), lds, s, (const T*)x, w49, bias, (const T*)res, (T*)y, H, W, C, flip, (T*)y2, y2scale);
     } else {
         constexpr int TH = 7, TW = 7, NT = 128;
         const size_t lds = (TH + 6) * (TW + 6) * kCSF * sizeof(T) + 49 * kCSF * 4;
-        dim3 grid(B * cdiv(H, TH) * cdiv(W, TW) * slices);
+        dim3 grid(sel.gx);
         hipLaunchKernelGGL((dwconv7_kernel<T, TH, TW, NT>), grid, dim3(NT), lds, s, (const T*)x, w49, bias,
                            (const T*)res, (T*)y, H, W, C, flip, (T*)y2, y2scale);
     }
     return ga_check_launch("ga_dwconv7");
 }
 
-void dwconv_wgrad_geometry(int B, int H, int W, int C, bool bf16, int* gx_out, int* nparts_out) {
-    const int slices = cdiv(C, kCSW);
-    const bool big = H % 14 == 0 && W % 14 == 0;
-    const long ntiles = big ? (long)B * (H / 14) * (W / 14) : (long)B * cdiv(H, 7) * cdiv(W, 7);
-    const bool dot2 = bf16 && C % 8 == 0;   // dot2 form: 89 KB of LDS at 14x14 -> one workgroup per CU
-    const int gx = (int)std::min<long>(ntiles, std::max(1, (big ? (dot2 ? 1 : 2) : 4) * ga_num_cus() / slices));
-    *gx_out = gx;
-    *nparts_out = gx * (big ? 2 : 1);          // one partial per (workgroup, group of 7 output rows)
-}
-
-// bytes of partial sums the backward-weight launch of this geometry needs (the larger of the forms that may serve it)
-size_t dwconv_wgrad_ws_bytes(int B, int H, int W, int C, bool bf16) {
-    int gx, nparts;
-    dwconv_wgrad_geometry(B, H, W, C, bf16, &gx, &nparts);
-    size_t need = (size_t)nparts * 50 * C * sizeof(float);
-    int R, wpu, nb;
-    if (bf16 && dww_rs_geometry(B, H, W, C, &R, &wpu, &nb)) need = std::max(need, (size_t)nb * DWW::NV * 64 * sizeof(float));
-    return need;
-}
-
 template <typename T>
 int launch_dwconv_wgrad(const void* dy, const void* x, float* dw49, float* dbias, int B, int H, int W, int C,
                         float* part, size_t ws_bytes, hipStream_t s) {
-    const int slices = cdiv(C, kCSW);
-    const bool big = H % 14 == 0 && W % 14 == 0;
-    const bool dot2 = sizeof(T) == 2 && C % 8 == 0;
-    int gx, nparts;
-    dwconv_wgrad_geometry(B, H, W, C, sizeof(T) == 2, &gx, &nparts);
-    const size_t need = dwconv_wgrad_ws_bytes(B, H, W, C, sizeof(T) == 2);
+    const DwwSel sel = dww_select(B, H, W, C, sizeof(T) == 2, ga_num_cus(), dw_knobs());
+    const int slices = sel.slices, gx = sel.gx, nparts = sel.nparts;
+    const bool big = sel.form == DWW_DOT2_14 || sel.form == DWW_SCALAR_14;
+    const size_t need = sel.ws_bytes;
     if (!part || ws_bytes < need) {
         ga_set_error("ga_dwconv7_bwd_weight: needs %zu B of caller-provided workspace (ga_dwconv7_bwd_weight_workspace), got %zu",
                      need, part ? ws_bytes : (size_t)0);
         return GA_ERR_BAD_ARG;
     }
     if constexpr (sizeof(T) == 2) {
-        int rsR, rsW, rsN;
-        // register-sliding form: 0 never, 1 (default) on 28 x 28 maps and larger (256 x 56 x 56 x 96: 0.134 vs 0.182 ms, 28 x 28 x 192:
-        // 0.071 vs 0.078; on the smaller maps its per-unit start-up and the 13 MB of partials eat the gain: 14 x 14 0.047 vs 0.044),
-        // 2 wherever it applies
-        const int use_rs = GA_KNOB("DWW_RS", 1);
-        if (use_rs && (use_rs == 2 || H * W >= 28 * 28) && dww_rs_geometry(B, H, W, C, &rsR, &rsW, &rsN))
-            return launch_dwconv_wgrad_rs(dy, x, dw49, dbias, B, H, W, C, part, s);
-        if (dot2) {
+        if (sel.form == DWW_RS_FORM) return launch_dwconv_wgrad_rs(dy, x, dw49, dbias, B, H, W, C, part, s, sel);
+        if (sel.form == DWW_DOT2_14 || sel.form == DWW_DOT2_7) {
             auto k14 = dwconv7_wgrad_dot2_kernel<14, 14>;
             auto k7 = dwconv7_wgrad_dot2_kernel<7, 7>;
             constexpr int lds14 = DWD<14, 14>::LDS;
@@ -1619,7 +1737,7 @@ int launch_dwconv_wgrad(const void* dy, const void* x, float* dw49, float* dbias
             else
                 hipLaunchKernelGGL(k7, dim3(gx, slices), dim3(G7::NT), G7::LDS, s, (const bf16_t*)dy,
                                    (const bf16_t*)x, part, B, H, W, C);
-            hipLaunchKernelGGL(dwconv7_wgrad_reduce, dim3(cdiv(50 * C, 64)), dim3(1024), 0, s, part, gx, C, dw49, dbias);
+            hipLaunchKernelGGL(dwconv7_wgrad_reduce, dim3(cdiv(50 * C, 64)), dim3(1024), 0, s, part, nparts, C, dw49, dbias);
             return ga_check_launch("ga_dwconv7_bwd_weight");
         }
     }
@@ -1676,7 +1794,22 @@ extern "C" int ga_dwconv7_bwd_data2(const void* dy, const float* w49, const void
 
 extern "C" size_t ga_dwconv7_bwd_weight_workspace(int B, int H, int W, int C, int dtype) {
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
-    return dwconv_wgrad_ws_bytes(B, H, W, C, dtype == GA_BF16);
+    return dww_select(B, H, W, C, dtype == GA_BF16, ga_num_cus(), dw_knobs()).ws_bytes;
+}
+
+extern "C" int ga_dwconv7_form(int B, int H, int W, int C, int dtype, int has_res, int has_y2, char* buf, size_t n) {
+    GA_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "ga_dwconv7_form: bad args (C%%4)");
+    GA_REQUIRE(has_res || !has_y2, "ga_dwconv7_form: bad args (the second output needs the residual form)");
+    if (buf && n)
+        dw_form_name(dw_select(B, H, W, C, dtype == GA_BF16, ga_num_cus(), dw_knobs()), dtype == GA_BF16, has_res != 0, has_y2 != 0,
+                     buf, n);
+    return GA_OK;
+}
+
+extern "C" int ga_dwconv7_bwd_weight_form(int B, int H, int W, int C, int dtype, char* buf, size_t n) {
+    GA_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "ga_dwconv7_bwd_weight_form: bad args (C%%4)");
+    if (buf && n) dww_form_name(dww_select(B, H, W, C, dtype == GA_BF16, ga_num_cus(), dw_knobs()), H, dtype == GA_BF16, buf, n);
+    return GA_OK;
 }
 
 extern "C" int ga_dwconv7_bwd_weight(const void* dy, const void* x, float* dw49, float* dbias, int B, int H, int W,

@@ -252,6 +252,31 @@ int ga_dwconv7_bwd_data2(const void* dy, const float* w49, const void* res, void
 size_t ga_dwconv7_bwd_weight_workspace(int B, int H, int W, int C, int dtype);
 int ga_dwconv7_bwd_weight(const void* dy, const void* x, float* dw49, float* dbias, int B, int H, int W, int C,
                           int dtype, void* workspace, size_t ws_bytes, ga_stream_t stream);
+/* Which kernel form the entry points above launch for a geometry under the current knob table, in the manner of ga_gemm_form:
+ * same validation of the geometry (GA_ERR_BAD_ARG with a message), on GA_OK the form's stable name in buf (NUL-terminated,
+ * truncated to n; buf may be NULL), no device memory touched, nothing launched, 256 compute units assumed without a GPU.  The
+ * launches run what the same host functions return (csrc/dwconv.hip: dw_select, dww_select), so the name is what runs.
+ *   ga_dwconv7_form (forward: has_res = has_y2 = 0; backward-data: has_res = res != NULL; _bwd_data2: both 1), as tried:
+ *     rs:R<r>:seg<s>:wpu<w>[+res][+y2]   register-sliding LDS-DMA form (bf16, C % 8 == 0, H % 7 == 0, below 2 GiB; knob DW_RS):
+ *                                        r rows per segment (DW_RS_ROWS, else the longest divisor of H that is a multiple of 7
+ *                                        with B s w >= 8 waves per CU), s = H / r segments per image, w waves per (image,
+ *                                        segment); +res / +y2 name the kernel instantiation
+ *     mfma:gx<g>:tiles<t>                Toeplitz form on the matrix cores (bf16, C % 8 == 0, H and W multiples of 14; knob
+ *                                        DW_MFMA: 2 always, 1 from 56 x 56 maps with t * ceil(C / 32) >= 16 per CU): g workgroups
+ *                                        per 32-channel slice walk t tiles; g is rounded down to a multiple of 8 from 16 (DW_XCD8)
+ *     dot2_14x14:gx<g>:tiles<t>          LDS-staged v_dot2 form on 14 x 14 tiles (bf16, C % 8 == 0, H and W multiples of 14)
+ *     dot2_7x7:gx<g>:tiles<t>            the same on 7 x 7 tiles (any H, W); g workgroups per 64-channel slice walk t tiles
+ *     scalar_14x14+f32|bf16              the scalar template (fp32; bf16 with C % 8 != 0), one workgroup per tile and 32 channels
+ *     scalar_7x7+f32|bf16
+ *   ga_dwconv7_bwd_weight_form:
+ *     rs:R<r>:seg<s>:wpu<w>:nbw<k>       register-sliding form (bf16, C % 8 == 0, H % 7 == 0, below 2 GiB; knob DWW_RS: 1 from
+ *                                        28 x 28 maps, 2 everywhere): k w workgroups of 4 waves, k = max(1, 2 CUs / w); the 4 k
+ *                                        waves of a lane map walk the B s units; r from DWW_RS_ROWS, else the longest with
+ *                                        B s >= 8 k
+ *     dot2_14x14:parts<p>  dot2_7x7:parts<p>            p workgroups per 64-channel slice, one partial each
+ *     scalar_14x14:parts<p>+f32|bf16  scalar_7x7:..     p partials of p / 2 (14 x 14) or p (7 x 7) workgroups per slice */
+int ga_dwconv7_form(int B, int H, int W, int C, int dtype, int has_res, int has_y2, char* buf, size_t n);
+int ga_dwconv7_bwd_weight_form(int B, int H, int W, int C, int dtype, char* buf, size_t n);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Depthwise 3x3 (pad 1, stride 1 or 2, no bias) convolution, NHWC [B][H][W][C] -> [B][Ho][Wo][C], Ho = (H - 1) / stride + 1

@@ -545,6 +545,8 @@ def test_weight_prep_fold_unfold(dt):
                                   (2, 28, 28, 40, 'mfma'), (2, 14, 14, 96, 'lds'), (1, 56, 56, 32, 'lds'), (3, 28, 21, 48, 'rs'),
                                   (5, 14, 14, 192, 'rs'), (2, 7, 7, 768, 'rs')])
 def test_dwconv7(dt, geom, knobs):
+    """every form once against fp32 conv2d, gated relative to the tensor's maximum; the edges of each form's launch geometry, per
+    element against float64 and with the form name asserted: tests/test_dwconv7_edges_gpu.py"""
     ops = _imp()
     if len(geom) == 5:
         if geom[4] == 'mfma':     # force the matrix-core (Toeplitz) form of the bf16 forward / backward-data kernel
