@@ -308,7 +308,7 @@ def config_string():
     # the host-side scheduling switches the engines read from the environment when they are built (engine.py: lanes, chains)
     host = sorted(k for k in os.environ if k.startswith(('GAEXT_', 'GA_FUSED_MLP')) and k != 'GAEXT_LIB')
     known = {'GAEXT_ASYNC_WGRAD', 'GAEXT_FWD_SPLIT', 'GAEXT_PAR_BRANCH', 'GAEXT_FWD_SKEW', 'GAEXT_FUSE_DP', 'GAEXT_HEAD_STREAMS',
-             'GA_FUSED_MLP', 'GAEXT_SMALL_SINGLE', 'GAEXT_SYNC_DEBUG', 'GAEXT_MLP_WG1'}
+             'GA_FUSED_MLP', 'GAEXT_SMALL_SINGLE', 'GAEXT_SYNC_DEBUG', 'GAEXT_MLP_WG1', 'GAEXT_MLP_PREFETCH'}
     for k in host:
         if k in known:
             s += f' host:{k}={os.environ[k]}'

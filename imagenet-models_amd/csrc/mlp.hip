@@ -81,7 +81,8 @@ __device__ __forceinline__ void rows_prefetch(PreArr<C, NTHR>& v, const bf16_t* 
 // fp32 accumulator tiles -> rows of Y through an LDS staging piece of 64 rows x (C + 4) floats, epilogue fused:
 //   y = R + rowscale * (acc + bias)
 // acc[tn][tm]: token row 16 tm + (lane & 15) of the wave's WROWS rows, columns wn * (C/2) + 16 tn + 4 (lane >> 4) .. +3
-template <int C, int NTHR, int NWM, int TM>
+// KEEP: the accumulators stay in their registers until the barrier behind their ds_writes (for callers with LDS-DMA in flight)
+template <int C, int NTHR, int NWM, int TM, bool KEEP = false>
 __device__ __forceinline__ void store_rows(float* Cs, const f32x4_t (&acc)[C / 32][TM], int wm, int wn, int lane, long m0, long M,
                                            const float* bias, const float* rowscale, int rps, bool has_r,
                                            const PreArr<C, NTHR>& pre, bf16_t* Y, long ldy, int tid) {
@@ -104,6 +105,10 @@ __device__ __forceinline__ void store_rows(float* Cs, const f32x4_t (&acc)[C / 3
                 }
         }
         __syncthreads();
+        if constexpr (KEEP) {
+#pragma unroll
+            for (int i = 0; i < (C / 32) * TM; ++i) asm volatile("" ::"v"(acc[i / TM][i % TM]));
+        }
         if (rg < RG) {
 #pragma unroll
             for (int it = 0; it < NR; ++it) {
@@ -309,16 +314,89 @@ __device__ __forceinline__ bf16x8_t tr_frag(const unsigned char* lo, const unsig
     return *reinterpret_cast<const bf16x8_t*>(&v[0]);
 }
 
-template <int C, int HC, bool WG>
+// PF (persistent form only, knob MLP_PREFETCH): the token rows of the NEXT tile of the walk travel while this one is computed.
+//   A second X image (LDS 120,320 -> 144,896 B of 163,840): the two images swap roles per tile.  At the top of tile t the rows
+//   of tile t + grid go into the spare image, and right behind the barrier that ends the last chunk's P1 -- the last reader of
+//   Ds -- the DY rows of tile t + grid go into Ds.  Both by LDS-DMA (buffer_load_dwordx4 ... lds): wave w fills rows
+//   16 w .. 16 w + 15 of each of the KS1 slabs, one 1 KiB wave-instruction per slab.  The DMA writes LDS lane-linearly, so the
+//   slab_off XOR layout is made on the SOURCE side: lane l lands in unit slot l & 3 of row l >> 2 and therefore fetches unit
+//   (l & 3) ^ ((l >> 4) & 3).  The buffer window is the tile's live rows exactly (base = row m0 of the operand, extent =
+//   (rows - 1) ld + C elements), every offset is the lane's (the scalar offset takes no part in the range check): rows >= M
+//   arrive as zeros, which is what stage_rows guarantees and the dW1 / dh = 0 reasoning above relies on.
+//   Waits: the X rows are issued BEFORE chunk 0's w_load, so the wait the compiler places for those registers ahead of
+//   w12_store retires them (vmcnt counts in order), and the barrier behind it shows them to every wave a whole tile before they
+//   are read.  The DY rows are younger than the last chunk's w_load: the vmcnt(0) ahead of that chunk's w3_store retires them
+//   (written out there as well), the barriers of the dx store and of the tile end follow.
+//   The dx staging piece moves from smem + 0 (over Xs / Ds, both in use now) into DHs / A2s, dead after the last P2.
+//   The first tile of a workgroup is staged by stage_rows as before.  No arithmetic changes: the same bits as PF = false.
+//   No ds_write follows a DMA issue closely (global loads, fragment reads and MFMAs do), and the registers of the P1 / dx
+//   staging ds_writes stay live up to the barrier behind them (the late ds_write data fetch recorded in DESIGN 5.3).
+//   mlp_bwd_kernel<96, 64, true, true> (-Rpass-analysis=kernel-resource-usage): 245 VGPRs, 0 AGPRs, no VGPR spill, no scratch,
+//   4 SGPRs spilled (to VGPR lanes: the two windows' scalars), 2 waves per SIMD; PF = false is instruction for instruction the
+//   kernel it was before (241 VGPRs).  Measured (profiles/mlp_bwd_phases.txt, mlp_prefetch_ab.txt): the row staging was 17 % of a
+//   stamped tile; 0.699 -> 0.633 ms per launch in the step.
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4_s;
+__device__ __forceinline__ u32x4_s rows_rsrc(const bf16_t* base, unsigned bytes) {
+    const unsigned long long a = reinterpret_cast<unsigned long long>(base);
+    u32x4_s r;
+    r[0] = __builtin_amdgcn_readfirstlane((unsigned)a);
+    r[1] = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);
+    r[2] = __builtin_amdgcn_readfirstlane(bytes);
+    r[3] = 0x00020000u;
+    return r;
+}
+// three LDS-DMA wave-instructions (64 lanes x 16 B each) to the wave-uniform LDS byte addresses dst, dst + 8 KiB, dst + 16 KiB
+// (one per k slab) from the lane offsets v0 .. v2 of the window rs.  M0 carries the destination and is written in the statement
+// that reads it; s_nop 4: the descriptor may come straight from v_readfirstlane.  Asm, so hipcc does not count the loads: see
+// "Waits" above
+__device__ __forceinline__ void dma_rows3(u32x4_s rs, unsigned v0, unsigned v1, unsigned v2, unsigned dst) {
+    unsigned keep;
+    asm volatile(
+        "s_nop 4\n\ts_mov_b32 %0, m0\n\t"
+        "s_mov_b32 m0, %5\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %4, 0 offen lds\n\t"
+        "s_mov_b32 m0, %6\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %4, 0 offen lds\n\t"
+        "s_mov_b32 m0, %7\n\ts_nop 0\n\tbuffer_load_dwordx4 %3, %4, 0 offen lds\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(v0), "v"(v1), "v"(v2), "s"(rs), "s"(dst), "s"(dst + 0x2000u), "s"(dst + 0x4000u)
+        : "memory");
+}
+
+#ifdef GAEXT_MLP_STAMPS
+constexpr int kMlpStamps = 5;     // stage, P1, P2 (+ dW1, a / dh rows, weight staging), dx store, tile-end barrier
+// diagnostic build (make libgaext_stamps.so, tools/mlp_phases.py): clock stamps at the phase boundaries of the persistent walk, summed per
+// workgroup and left behind the partials.  The fences forbid overlaps the real kernel has: read the shares, not the length
+__device__ __forceinline__ unsigned long long mlp_stamp() {
+    unsigned long long t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+#define MLP_STAMP(k)                                  \
+    do {                                              \
+        const unsigned long long t_ = mlp_stamp();    \
+        if constexpr (WG) st_sum[k] += t_ - st_prev;  \
+        st_prev = t_;                                 \
+    } while (0)
+#else
+#define MLP_STAMP(k) \
+    do {             \
+    } while (0)
+#endif
+
+template <int C, int HC, bool WG, bool PF = false>
 __global__ __launch_bounds__(512, 1) void mlp_bwd_kernel(const ga_mlp_bwd_desc d) {
     constexpr int KS1 = C / 32, KS2 = HC / 32, TN1 = HC / 32, TN2 = C / 32;
     constexpr int XS = KS1 * BM * 64, WS = KS1 * HC * 64, TS = KS2 * BM * 64;
     constexpr int NPC = HC * C / 8, NI = (NPC + 511) / 512;     // 16-byte pieces per weight chunk / per thread
     constexpr int NCH = 4 * C / HC;                             // chunks of the hidden dimension (H = 4C)
     static_assert(!WG || (HC == 64 && C == 96), "the in-kernel weight gradient is laid out for 4 x 6 tiles over 8 waves");
+    static_assert(!PF || (WG && KS1 == 3), "the prefetch belongs to the persistent walk; dma_rows3 fills three slabs");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* Xs = smem;
-    unsigned char* Ds = Xs + XS;
+    // PF: X images at 0 and XS; xoff = the one this tile reads (every DMA destination stays below 72 KiB)
+    unsigned xoff = 0;
+    unsigned char* Ds = smem + (PF ? 2 : 1) * XS;
     unsigned char* W1s = Ds + XS;
     unsigned char* W2Ts = W1s + WS;
     unsigned char* W1Ts = W2Ts + WS;          // [C][HC]: KS2 slabs of C rows
@@ -388,22 +466,47 @@ __global__ __launch_bounds__(512, 1) void mlp_bwd_kernel(const ga_mlp_bwd_desc d
     for (int i = tid; i < 4 * C; i += 512) B1s[i] = d.b1[i];
     const long ntiles = (d.M + BM - 1) / BM;
     long tile = blockIdx.x;
-    w_load(0);
-    while (true) {
-        const long m0 = tile * BM;
-        const bool first = !WG || tile == (long)blockIdx.x;
-        const bool next_tile = WG && tile + (long)gridDim.x < ntiles;
-        // WG: the per-tile addressing (row staging, DX rows) is derived from a copy of the thread index that the compiler cannot
-        // see through, so it is re-computed per tile and not kept -- spilled -- across the whole tile walk
+#ifdef GAEXT_MLP_STAMPS
+    unsigned long long st_sum[kMlpStamps] = {0, 0, 0, 0, 0}, st_prev = mlp_stamp();
+#endif
+    // PF: the 128 rows of tile t + grid of `src` -> the slab images at `dst`; rows >= M read as zeros (window = the live rows)
+    auto dma_next = [&](const void* src, long ld, unsigned char* dst) __attribute__((always_inline)) {
+        const long mn = (tile + (long)gridDim.x) * BM;
+        const long live = d.M - mn < BM ? d.M - mn : BM;
+        const u32x4_s rs = rows_rsrc(reinterpret_cast<const bf16_t*>(src) + mn * ld, (unsigned)(((live - 1) * ld + C) * 2));
+        int dtid = tid;
+        asm volatile("" : "+v"(dtid));
+        const int l = dtid & 63;
+        const unsigned v = (unsigned)((16 * wu + (l >> 2)) * (int)ld * 2 + (((l & 3) ^ ((l >> 4) & 3)) << 4));
+        const unsigned lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)dst;
+        dma_rows3(rs, v, v + 64, v + 128, __builtin_amdgcn_readfirstlane(lds + wu * 1024));
+    };
+    // the rows of tile m0 through registers, with the workgroup's first tile the weights of chunk 0 (later tiles: staged by the
+    // previous tile's last chunk).  WG: the per-tile addressing (row staging, DX rows) is derived from a copy of the thread index
+    // that the compiler cannot see through, so it is re-computed per tile and not kept -- spilled -- across the whole tile walk
+    auto stage_tile = [&](unsigned char* Xs, const long m0, const bool first) __attribute__((always_inline)) {
         int ttid = tid;
         if constexpr (WG) asm volatile("" : "+v"(ttid));
         stage_rows<BM, KS1, 512>(Xs, reinterpret_cast<const bf16_t*>(d.X), d.ldx, m0, d.M, ttid);
         stage_rows<BM, KS1, 512>(Ds, reinterpret_cast<const bf16_t*>(d.DY), d.lddy, m0, d.M, ttid);
-        if (first) {                           // later tiles: chunk 0 of the weights was staged by the previous tile's last chunk
+        if (first) {
             w12_store();
             w3_store();
         }
         __syncthreads();
+    };
+    w_load(0);
+    if constexpr (PF) stage_tile(smem, tile * BM, true);      // every later tile arrives by DMA
+    while (true) {
+        const long m0 = tile * BM;
+        const bool next_tile = WG && tile + (long)gridDim.x < ntiles;
+        unsigned char* const Xs = smem + xoff;
+        if constexpr (!PF) stage_tile(Xs, m0, !WG || tile == (long)blockIdx.x);
+        MLP_STAMP(0);
+        // (PF, later tiles: the rows came by DMA and the tile-end barrier below has shown them to every wave)
+        if constexpr (PF) {
+            if (next_tile) dma_next(d.X, d.ldx, smem + (xoff ^ XS));
+        }
 
         f32x4_t dx[TN2][2];
 #pragma unroll
@@ -433,10 +536,12 @@ __global__ __launch_bounds__(512, 1) void mlp_bwd_kernel(const ga_mlp_bwd_desc d
                 }
             }
         };
-        auto chunk = [&](const int j0, const bool more, const int jn) __attribute__((always_inline)) {
+        // dy_next (PF): this is the tile's last chunk and the walk goes on -- Ds is refilled behind the P1 barrier
+        auto chunk = [&](const int j0, const bool more, const int jn, const bool dy_next) __attribute__((always_inline)) {
             if (more) w_load(jn);
             // ---- P1
             f32x4_t h[TN1][2], t[TN1][2];
+            [[maybe_unused]] uint2 pkeep[TN1][2][2];
 #pragma unroll
             for (int i = 0; i < TN1; ++i)
 #pragma unroll
@@ -480,12 +585,22 @@ __global__ __launch_bounds__(512, 1) void mlp_bwd_kernel(const ga_mlp_bwd_desc d
                     p.x = pack2bf(a[0], a[1]);
                     p.y = pack2bf(a[2], a[3]);
                     *reinterpret_cast<uint2*>(A2s + o) = p;
+                    if constexpr (PF) pkeep[tn][tm][0] = p;
                     p.x = pack2bf(dh[0], dh[1]);
                     p.y = pack2bf(dh[2], dh[3]);
                     *reinterpret_cast<uint2*>(DHs + o) = p;
+                    if constexpr (PF) pkeep[tn][tm][1] = p;
                 }
             }
             lds_barrier();                       // A2s / DHs complete; W1s / W2Ts are free
+            if constexpr (PF) {
+                // the written pieces stay in their registers until the writes are done (X rows may still be arriving by DMA)
+#pragma unroll
+                for (int i = 0; i < TN1 * 4; ++i) asm volatile("" ::"v"(pkeep[i >> 2][(i >> 1) & 1][i & 1].x), "v"(pkeep[i >> 2][(i >> 1) & 1][i & 1].y));
+                // Ds had its last reader in the P1 above
+                if (dy_next) dma_next(d.DY, d.lddy, Ds);
+            }
+            MLP_STAMP(1);
             // ---- P2
 #pragma unroll
             for (int ks = 0; ks < KS2; ++ks) {
@@ -533,25 +648,50 @@ __global__ __launch_bounds__(512, 1) void mlp_bwd_kernel(const ga_mlp_bwd_desc d
             if (more) w12_store();
             lds_barrier();                       // A2s / DHs / W1Ts are free, the new W1s / W2Ts visible
             if (more) w3_store();
+            if constexpr (PF) {
+                // counts every vector memory operation of the wave, and adds no wait: w3_store has just waited for the youngest
+                // weight register with vmcnt(0) (the a / dh stores behind it are conditional, so the compiler counts none).
+                // Written out because the DY rows, issued BEHIND this chunk's w_load, are retired by that wait alone; the
+                // store_rows barriers and the tile-end barrier then show them to every wave
+                if (dy_next) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            MLP_STAMP(2);
         };
         for (int j0 = 0; j0 < d.H; j0 += HC) {
             const bool last = j0 + HC >= d.H;
-            chunk(j0, !last || next_tile, last ? 0 : j0 + HC);
+            // PF: chunk 0's weights are staged behind the workgroup's last chunk as well (unused).  With `more` a constant the
+            // compiler follows the weight registers from load to store on one path; as a condition it sees loads pending at
+            // the head of the next chunk and drains vmcnt there -- the rows in flight with it
+            chunk(j0, PF || !last || next_tile, last ? 0 : j0 + HC, last && next_tile);
         }
         u32x4_t nopre[BM / 64][RowPre<C, 512>::NR];
 #pragma unroll
         for (int i = 0; i < BM / 64; ++i)
 #pragma unroll
             for (int j = 0; j < RowPre<C, 512>::NR; ++j) nopre[i][j] = u32x4_t{0, 0, 0, 0};
-        // (the staging piece covers Xs and the head of Ds only: the weights staged for the next tile are beyond it)
+        // (the staging piece covers Xs and the head of Ds only: the weights staged for the next tile are beyond it.
+        //  PF: it lies in DHs / A2s, 25,600 of their 32,768 bytes -- Xs, the spare image and Ds all hold or receive rows)
+        static_assert(!PF || 64 * (C + 4) * 4 <= 2 * TS, "the dx staging piece must fit into DHs + A2s");
         int stid = tid;
         if constexpr (WG) asm volatile("" : "+v"(stid));
-        store_rows<C, 512, 4, 2>(reinterpret_cast<float*>(smem), dx, stid >> 7, (stid >> 6) & 1, stid & 63, m0, d.M, nullptr, nullptr, 1,
-                                 false, nopre, reinterpret_cast<bf16_t*>(d.DX), d.lddx, stid);
+        store_rows<C, 512, 4, 2, PF>(reinterpret_cast<float*>(PF ? DHs : smem), dx, stid >> 7, (stid >> 6) & 1, stid & 63, m0, d.M, nullptr,
+                                     nullptr, 1, false, nopre, reinterpret_cast<bf16_t*>(d.DX), d.lddx, stid);
+        MLP_STAMP(3);
         if (!next_tile) break;
+        if constexpr (PF) xoff ^= XS;
         tile += gridDim.x;
-        __syncthreads();                         // the staging piece has been read: Xs / Ds may be staged again
+        __syncthreads();                         // the staging piece has been read: Xs / Ds may be staged again (PF: hold the rows)
+        MLP_STAMP(4);
     }
+#ifdef GAEXT_MLP_STAMPS
+    if constexpr (WG) {
+        // behind the partials of all workgroups, where the caller left the room (tools/mlp_phases.py does)
+        unsigned long long* sp = reinterpret_cast<unsigned long long*>(d.partials + (long)gridDim.x * (4 * C * C + 4 * C)) +
+                                 (long)blockIdx.x * kMlpStamps;
+        if (tid == 0 && d.partials_bytes >= (size_t)gridDim.x * ((4 * C * C + 4 * C) * sizeof(float) + kMlpStamps * 8))
+            for (int i = 0; i < kMlpStamps; ++i) sp[i] = st_sum[i];
+    }
+#endif
     if constexpr (WG) {
         // lane: channel = column (lane & 15) of the tile, hidden rows 4 g + r
         float* P = d.partials + (long)blockIdx.x * (4 * C * C + 4 * C);
@@ -691,7 +831,16 @@ extern "C" int ga_mlp_bwd(const ga_mlp_bwd_desc* d, ga_stream_t stream) {
         const int n = d->H * d->C + d->H;
         GA_REQUIRE(d->partials_bytes >= (size_t)grid * n * sizeof(float), "ga_mlp_bwd: partials holds %zu bytes, %zu needed (ga_mlp_bwd_partials)",
                    (size_t)d->partials_bytes, (size_t)grid * n * sizeof(float));
-        hipLaunchKernelGGL((mlp_bwd_kernel<96, 64, true>), dim3(grid), dim3(512), lds, s, *d);
+        // MLP_PREFETCH (default 1): the next tile's rows travel by LDS-DMA during this one (PF above); 0: every tile through
+        // stage_rows.  Same grid, same tile walk, same bits
+        if (GA_KNOB("MLP_PREFETCH", 1)) {
+            constexpr int lds_pf = lds + (96 / 32) * BM * 64;          // the second X image
+            static const bool pf_ok = set_lds(mlp_bwd_kernel<96, 64, true, true>, lds_pf);
+            GA_REQUIRE(pf_ok, "ga_mlp_bwd: LDS (MLP_PREFETCH)");
+            hipLaunchKernelGGL((mlp_bwd_kernel<96, 64, true, true>), dim3(grid), dim3(512), lds_pf, s, *d);
+        } else {
+            hipLaunchKernelGGL((mlp_bwd_kernel<96, 64, true>), dim3(grid), dim3(512), lds, s, *d);
+        }
         hipLaunchKernelGGL(mlp_bwd_wg_reduce_kernel, dim3((n / 4 + 63) / 64), dim3(256), 0, s, d->partials, grid, n, d->H * d->C, d->C,
                            d->dW1, (long)d->ldw, d->db1);
         return ga_check_launch("ga_mlp_bwd");
