@@ -40,3 +40,5 @@ from .input_stage import InputStage  # noqa: E402,F401
 from .trainer import TrainStep, distribute_bn, make_buckets  # noqa: E402,F401
 from .comm import NativeComm  # noqa: E402,F401
 from .checkpoint import save_checkpoint, load_checkpoint, ModelEma  # noqa: E402,F401
+from .checkpoint import (read_checkpoint, resume_checkpoint, capture_train_state, restore_train_state,  # noqa: E402,F401
+                         saved_initial_seed, CheckpointSaver, DeviceSnapshot)

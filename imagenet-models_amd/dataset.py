@@ -73,12 +73,20 @@ class FolderLoader:
             raise ValueError(f'FolderLoader: batch {batch}, rank {rank} of {world}, prefetch {prefetch}')
         self.dataset, self.batch, self.decoder, self.train = dataset, int(batch), decoder, bool(train)
         self.seed, self.rank, self.world, self.prefetch, self.device = int(seed), int(rank), int(world), int(prefetch), device
-        self.epoch = 0
+        self.epoch = self.start_batch = 0
         if self.train and len(self) == 0:
             raise ValueError(f'FolderLoader: {len(dataset)} samples over {world} rank(s) give no full batch of {batch}')
 
-    def set_epoch(self, epoch):
-        self.epoch = int(epoch)
+    def set_epoch(self, epoch, start_batch=0):
+        """start_batch: the next iteration yields batches(epoch)[start_batch:] -- a run resumed inside an epoch; the skipped
+        batches' files are neither read nor decoded"""
+        if not 0 <= int(start_batch) <= len(self):
+            raise ValueError(f'FolderLoader: start_batch {start_batch} of an epoch of {len(self)} batches')
+        self.epoch, self.start_batch = int(epoch), int(start_batch)
+
+    def plan(self):
+        """what the next iteration reads, decodes and yields: batches() of the epoch from the start position on"""
+        return self.batches()[self.start_batch:]
 
     def indices(self, epoch=None):
         """this rank's sample indices of an epoch, in order.  Training: the epoch's permutation cut to a multiple of world * batch
@@ -127,7 +135,7 @@ class FolderLoader:
             q.put(e)
 
     def __iter__(self):
-        plan = self.batches()
+        plan = self.plan()
         q, stop = queue.Queue(maxsize=self.prefetch), threading.Event()
         stream = torch.cuda.Stream(device=torch.device(self.device))       # the producer's copies and launches: the step's stream waits per batch
         t = threading.Thread(target=self._produce, args=(plan, q, stop, stream), name='folder-loader', daemon=True)

@@ -81,6 +81,8 @@ class _FlatOptimizer:
 
 
 class FusedSGD(_FlatOptimizer):
+    kind, moment_names = 'sgd', ('buf',)
+
     def __init__(self, model, lr=0.1, momentum=0.9, weight_decay=0.0, nesterov=True):
         super().__init__(model, lr, weight_decay)
         self.momentum, self.nesterov = momentum, nesterov
@@ -112,9 +114,12 @@ class FusedSGD(_FlatOptimizer):
         self.steps = sd['steps']
         self.buf.copy_(sd['buf'])
         self.param_groups[0].update(sd['param_groups'][0])
+        self._hp_host = None         # the next step pushes its row afresh: the bias corrections of step `steps` + 1
 
 
 class FusedAdamW(_FlatOptimizer):
+    kind, moment_names = 'adamw', ('m', 'v')
+
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
         super().__init__(model, lr, weight_decay)
         self.betas, self.eps = betas, eps
@@ -151,11 +156,13 @@ class FusedAdamW(_FlatOptimizer):
         self.m.copy_(sd['m'])
         self.v.copy_(sd['v'])
         self.param_groups[0].update(sd['param_groups'][0])
+        self._hp_host = None         # the next step pushes its row afresh: the bias corrections of step `steps` + 1
 
 
 class FusedLamb(_FlatOptimizer):
     """timm.optim.Lamb (bias correction, grad averaging, max_grad_norm 1.0, trust ratio where weight decay applies) -- the
     optimizer of the published GA recipes (GA/README.md:26).  timm is un-vendored: semantics restated, parity unpinned."""
+    kind, moment_names = 'lamb', ('m', 'v')
     CHUNK = 16384
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, max_grad_norm=1.0,
@@ -203,6 +210,7 @@ class FusedLamb(_FlatOptimizer):
         self.m.copy_(sd['m'])
         self.v.copy_(sd['v'])
         self.param_groups[0].update(sd['param_groups'][0])
+        self._hp_host = None         # the next step pushes its row afresh: the bias corrections of step `steps` + 1
 
 
 def create_optimizer_v2(model, opt='sgd', lr=None, weight_decay=0., momentum=0.9, eps=None, betas=None, **_):

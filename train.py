@@ -11,9 +11,14 @@ oracle timed by bench.py).
   python train.py /data/imagenet --model map_resnet50 -b 256 -j 8 --aa rand-m9-mstd0.5-inc1 --collate-mixup --reprob 0.25
       an image folder (DIR/train/<class>/*.jpg, DIR/validation/...): baseline JPEGs are entropy-decoded on -j host threads and
       rebuilt, cropped, resized and augmented on the device
+  python train.py /data/imagenet ... --output out --recovery-interval 500      out/last.pth.tar, checkpoint-N, model_best, and a recovery
+      file every 500 optimizer steps, written behind the step
+  python train.py /data/imagenet ... --output out --resume out/last.pth.tar    continue exactly: weights, optimizer, EMA, every random
+      stream and the loader position (a recovery file resumes inside its epoch; the reference restarts at the next one)
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train.py --synthetic ...
 """
 import argparse
+import contextlib
 import logging
 import os
 import random
@@ -117,6 +122,21 @@ parser.add_argument('--device', default='cuda')
 parser.add_argument('--seed', type=int, default=42)
 parser.add_argument('--log-interval', type=int, default=50)
 parser.add_argument('--output', default='')
+# checkpoints and resuming (GA/train.py:96-99,269,485-526,633-693,810-812; MAP/train.py has the same flags)
+parser.add_argument('--resume', default='', type=str, metavar='PATH', help='Resume full model and optimizer state from checkpoint; with the '
+                    "file's train_state every random stream and the loader position too (default: none)")
+parser.add_argument('--no-resume-opt', action='store_true', default=False, help='prevent resume of optimizer state when resuming model: '
+                    'weights (and EMA) and epoch only')
+parser.add_argument('--start-epoch', default=None, type=int, metavar='N', help='manual epoch number (useful on restarts); overrides the '
+                    'epoch of --resume')
+parser.add_argument('--initial-checkpoint', default='', type=str, metavar='PATH', help='Initialize model from this checkpoint (weights '
+                    'only; default: none)')
+parser.add_argument('--recovery-interval', type=int, default=0, metavar='N', help='write a recovery checkpoint every N optimizer steps '
+                    'and at the last batch of an epoch, behind the step; only the newest is kept (default: 0, none)')
+parser.add_argument('--checkpoint-hist', type=int, default=None, metavar='N', help='number of best epoch checkpoints to keep (default: '
+                    'all of them -- the reference keeps 10; every epoch file stays, as it did before this flag existed)')
+parser.add_argument('--eval-metric', default='top1', type=str, metavar='EVAL_METRIC', help='Best metric: "top1", "top5" or "loss" (the '
+                    'epoch\'s training loss, lower is better: the evaluation loops compute none) (default: "top1")')
 parser.add_argument('--local_rank', default=0, type=int)
 
 
@@ -129,12 +149,18 @@ class SyntheticLoader:
         self.g = torch.Generator(device=device).manual_seed(seed)
         self.device = device
         self.ragged = synthetic_ragged(batch, source, seed, device) if source is not None else None
+        self.start_batch = 0
 
     def __len__(self):
         return self.steps
 
+    def set_epoch(self, epoch, start_batch=0):
+        """the next iteration yields the batches from `start_batch` on (a run resumed inside an epoch: the generator `g` continues
+        from its restored state, the epoch number plays no part)"""
+        self.start_batch = int(start_batch)
+
     def __iter__(self):
-        for _ in range(self.steps):
+        for _ in range(self.start_batch, self.steps):
             if self.ragged is not None:
                 yield self.ragged, torch.randint(0, self.nc, (self.batch,), device=self.device, generator=self.g)
                 continue
@@ -157,15 +183,21 @@ class AverageMeter:
         self.avg = self.sum / self.count
 
 
-def train_one_epoch(epoch, step_fn, loader, args, world, rank, model_ema=None):
+def train_one_epoch(epoch, step_fn, loader, args, world, rank, model_ema=None, saver=None, start_batch=0):
     batch_time_m, losses_m = AverageMeter(), AverageMeter()
     end = time.time()
     last_idx = len(loader) - 1
     loss = None
-    for batch_idx, (x, y) in enumerate(loader):
+    for batch_idx, (x, y) in enumerate(loader, start_batch):
         loss = step_fn(x, y)
-        if model_ema is not None and step_fn.micro % step_fn.accum == 0:   # after every optimizer step (GA/train.py:774)
+        boundary = step_fn.micro % step_fn.accum == 0
+        if model_ema is not None and boundary:   # after every optimizer step (GA/train.py:774)
             model_ema.update()
+        # recovery points at optimizer-step boundaries only (no partial gradient to save): a device snapshot, written behind
+        if args.recovery_interval and args.output and boundary and (step_fn.opt.steps % args.recovery_interval == 0 or batch_idx == last_idx):
+            state = A.capture_train_state(step_fn, loader, epoch, batch_idx + 1, rank, world, device_counters=False)
+            if saver is not None:
+                saver.take(epoch, train_state=state, recovery_batch=batch_idx)
         if batch_idx % args.log_interval == 0 or batch_idx == last_idx:
             torch.cuda.synchronize()
             lv = loss.detach().clone()
@@ -238,7 +270,34 @@ def main():
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', str(args.local_rank)))
+    if args.eval_metric not in ('top1', 'top5', 'loss'):
+        raise SystemExit(f"train.py: --eval-metric {args.eval_metric!r}: 'top1', 'top5' or 'loss'")
+    if args.checkpoint_hist is not None and args.checkpoint_hist < 1:
+        raise SystemExit(f'train.py: --checkpoint-hist {args.checkpoint_hist}: at least 1')
+    # the files are read here, on the host: one that is missing or does not load ends the run before the device is touched
+    resume_ck = None
+    for flag, path in (('--resume', args.resume), ('--initial-checkpoint', args.initial_checkpoint)):
+        if not path:
+            continue
+        if not os.path.isfile(path):
+            raise SystemExit(f'train.py: {flag} {path!r}: no such file')
+        try:
+            ck = A.read_checkpoint(path)
+        except Exception as e:
+            raise SystemExit(f'train.py: {flag} {path!r} does not load: {e}')
+        if flag == '--resume':
+            if not isinstance(ck, dict) or 'state_dict' not in ck:
+                raise SystemExit(f"train.py: --resume {path!r} is not a training checkpoint (no 'state_dict' key)")
+            resume_ck = ck
+        del ck
+    resume_state = resume_ck.get('train_state') if (resume_ck is not None and not args.no_resume_opt) else None
+    if resume_state is not None and resume_state['world_size'] != world:
+        raise SystemExit(f"train.py: --resume {args.resume!r} was written by {resume_state['world_size']} rank(s), this run has {world}: "
+                         'the per-rank generator states and the loader position do not carry over (--no-resume-opt takes the weights '
+                         'and the epoch only)')
     torch.manual_seed(args.seed + rank)
+    if resume_state is not None:             # the DropPath / dropout samplers are keyed by torch.initial_seed() when the engine is built
+        torch.manual_seed(A.saved_initial_seed(resume_state, rank))
     np.random.seed(args.seed + rank)          # timm random_seed(): mixup draws lam / boxes from numpy's global generator
     random.seed(args.seed + rank)             # ... and RandomErasing draws its boxes from Python's
     model = A.create_model(args.model, pretrained=False, num_classes=args.num_classes, drop_path_rate=args.drop_path,
@@ -271,6 +330,8 @@ def main():
         else:
             dist.init_process_group(backend, init_method='env://')
     model = model.cuda()
+    if args.initial_checkpoint:
+        A.load_checkpoint(model, args.initial_checkpoint)
     if world > 1:
         dist.broadcast(model.flat_state()['params'], 0)
         dist.broadcast(model.flat_state()['buffers'], 0)
@@ -335,33 +396,68 @@ def main():
         loader = SyntheticLoader(args.batch_size, args.steps_per_epoch, model.num_classes, args.seed + rank, 'cuda', img,
                                  uint8=step_fn.input_stage.takes == 'uint8', source=source)
         eval_loader = SyntheticLoader(args.batch_size, max(1, args.steps_per_epoch // 10), model.num_classes, 7 + rank, 'cuda', img)
+    start_epoch = start_batch = 0
+    if resume_ck is not None:
+        start_epoch, start_batch = A.resume_checkpoint(resume_ck, model, opt, model_ema, step_fn, loader, rank, world,
+                                                       resume_opt=not args.no_resume_opt)
+        resume_ck = resume_state = None
+    if args.start_epoch is not None:
+        start_epoch, start_batch = args.start_epoch, 0
+    if sched is not None:
+        sched.step(start_epoch)
+    if args.resume and rank == 0:
+        _logger.info('Resumed %s: starting at epoch %d, batch %d of %d, lr %.6e', args.resume, start_epoch, start_batch, len(loader),
+                     opt.param_groups[0]['lr'])
+    saver = None
+    if args.output and rank == 0:
+        saver = A.CheckpointSaver(args.output, A.DeviceSnapshot(model, opt, model_ema, step_fn), arch=args.model,
+                                  eval_metric=args.eval_metric, checkpoint_hist=args.checkpoint_hist)
     model.train()
-    for epoch in range(args.epochs):
+    # leaving this block -- the normal end or an exception -- waits for the write in flight; the writer's own exception is raised here
+    with saver if saver is not None else contextlib.nullcontext():
+        train_loop(args, model, opt, sched, step_fn, model_ema, loader, eval_loader, eval_crop, decoder, folder, mixup_fn or collate_mixup,
+                   saver, start_epoch, start_batch, world, rank)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def evaluate(model, eval_loader, eval_crop, args, world, folder):
+    return validate_folder(model, eval_loader, eval_crop, world) if folder is not None else validate(model, eval_loader, args, world)
+
+
+def train_loop(args, model, opt, sched, step_fn, model_ema, loader, eval_loader, eval_crop, decoder, folder, mixup, saver, start_epoch,
+               start_batch, world, rank):
+    for epoch in range(start_epoch, args.epochs):
         if sched is not None:
             sched.step(epoch)
-        if (mixup_fn or collate_mixup) is not None and args.mixup_off_epoch and epoch >= args.mixup_off_epoch:
-            (mixup_fn or collate_mixup).mixup_enabled = False      # GA/train.py:705-709, MAP/train.py:846-850
-        if folder is not None:
-            loader.set_epoch(epoch)
-        train_metrics = train_one_epoch(epoch, step_fn, loader, args, world, rank, model_ema)
+        if mixup is not None and args.mixup_off_epoch and epoch >= args.mixup_off_epoch:
+            mixup.mixup_enabled = False      # GA/train.py:705-709, MAP/train.py:846-850
+        first = start_batch if epoch == start_epoch else 0       # a recovery file resumes inside its epoch
+        loader.set_epoch(epoch, first)
+        train_metrics = train_one_epoch(epoch, step_fn, loader, args, world, rank, model_ema, saver, first)
         if world > 1 and args.dist_bn in ('broadcast', 'reduce'):
             A.distribute_bn(model, world, args.dist_bn == 'reduce')
-        if folder is not None:
-            eval_metrics = validate_folder(model, eval_loader, eval_crop, world)
-            if rank == 0:
-                _logger.info('    evaluated %d images; %d of %d files so far went through the PIL fallback', eval_metrics['samples'],
-                             decoder.fallbacks, decoder.decoded)
-        else:
-            eval_metrics = validate(model, eval_loader, args, world)
+        eval_metrics = evaluate(model, eval_loader, eval_crop, args, world, folder)
+        if folder is not None and rank == 0:
+            _logger.info('    evaluated %d images; %d of %d files so far went through the PIL fallback', eval_metrics['samples'],
+                         decoder.fallbacks, decoder.decoded)
         if rank == 0:
             _logger.info('*** epoch %d: train loss %.4f  top1 %.3f  top5 %.3f', epoch, train_metrics['loss'],
                          eval_metrics['top1'], eval_metrics['top5'])
-            if args.output:
-                os.makedirs(args.output, exist_ok=True)
-                A.save_checkpoint(model, opt, epoch, os.path.join(args.output, f'checkpoint-{epoch}.pth.tar'),
-                                  metric=eval_metrics['top1'], arch=args.model, model_ema=model_ema)
-    if world > 1:
-        dist.destroy_process_group()
+        if model_ema is not None:
+            # the EMA weights evaluated in the model's place; the checkpoint is selected by their metric (GA/train.py:675-679)
+            with model_ema.swapped():
+                if world > 1 and args.dist_bn in ('broadcast', 'reduce'):      # distribute_bn of the EMA's statistics (:672-674)
+                    A.distribute_bn(model, world, args.dist_bn == 'reduce')
+                eval_metrics = evaluate(model, eval_loader, eval_crop, args, world, folder)
+            if rank == 0:
+                _logger.info('*** epoch %d (EMA): top1 %.3f  top5 %.3f', epoch, eval_metrics['top1'], eval_metrics['top5'])
+        if args.output:
+            state = A.capture_train_state(step_fn, loader, epoch, len(loader), rank, world, device_counters=False)
+            if saver is not None:
+                metric = train_metrics['loss'] if args.eval_metric == 'loss' else eval_metrics[args.eval_metric]
+                best, best_epoch = saver.take(epoch, metric=metric, train_state=state)
+                _logger.info('    checkpoint of epoch %d queued; best %s so far %.4f (epoch %d)', epoch, args.eval_metric, best, best_epoch)
 
 
 if __name__ == '__main__':
