@@ -194,24 +194,22 @@ class ConvNeXtTrunk:
         dp = self.dp_scale.get(pre)
         dyz = dy
         par, dz_tag = '', 'dyz'
-        if self.async_wgrad and Bk.lane == 0:
+        # the weight-gradient launches read only what the dgrad chain has already produced and nothing on the chain
+        # reads their results: on the trunk they go to the plan's asynchronous lane and fill the tails of the chain's
+        # launches (the next block joins before it overwrites dyz / dh / du)
+        side = self._wgrad_window()
+        if side:
             # two sets of the transients the weight-gradient launches read (dh, du; three of dyz; the caller rotates
             # three dx buffers): this block only has to wait for the asynchronous launches of the block before the
             # previous one
-            self._bwd_seq += 1
             par = str(self._bwd_seq & 1)
             dz_tag = f'dyz{self._bwd_seq % 3}'
-            Bk.join_async(f'blk{self._bwd_seq - 2}')
         if dp is not None:
             if pre in self._pre_dyz:
                 dyz = self._pre_dyz.pop(pre)          # written by the previous block's depthwise backward
             else:
                 dyz = self.tmp(dz_tag, (M, C))
                 Bk.rowscale(dy, dp, dyz, M * C, res * res * C, dt, label=pre + 'dp')
-        # the weight-gradient launches read only what the dgrad chain has already produced and nothing on the chain
-        # reads their results: on the trunk they go to the plan's asynchronous lane and fill the tails of the chain's
-        # launches (the next block joins before it overwrites dyz / dh / du)
-        side = self.async_wgrad and Bk.lane == 0
         wl = ASYNC_LANE if side else Bk.lane
         ml = Bk.lane
         G2, gb2 = self.gbuf((C, 4 * C)), self.gbuf((C,))
@@ -258,8 +256,7 @@ class ConvNeXtTrunk:
         Bk.lane = wl
         Bk.dwconv7_bwd_weight(du, b['x'], dw49, self.grad(pre + self.NAMES['dw'] + 'bias'), B, res, res, C, dt, label=pre + 'dww')
         Bk.lane = ml
-        if side:
-            Bk.async_mark(f'blk{self._bwd_seq}')
+        self._wgrad_window_mark(side)
         dx2 = dp_next = None
         if next_pre is not None and self.fuse_dp:
             dp_next = self.dp_scale.get(next_pre)

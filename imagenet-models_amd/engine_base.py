@@ -11,7 +11,7 @@ Data layout in HBM (bf16 mode; fp32 mode is identical with 4-byte elements):
     directly into it or into a zeroed scratch arena of effective-weight gradients that ga_weight_unfold maps back.
 
 A family is `class XEngine(<builders...>, EngineBase)`: the builders (engine.ConvNeXtTrunk / GroupMlp / GAHeads, engine_map.MAPHead,
-engine_vit.ViTBlocks, engine_pit.PiTTrunk) are stateless classes of recording methods -- no __init__, attributes created by their own
+engine_blocks.TransformerBlocks, engine_pit.PiTTrunk) are stateless classes of recording methods -- no __init__, attributes created by their own
 build methods only -- and the family fills in the hooks `_drop_path_rates`, `_build` and, where it needs more gradient scratch,
 `_arena_extra`.  The constructor runs `_build()` and then the tail every plan ends with (`_finish`).
 
@@ -174,6 +174,21 @@ class EngineBase:
             yield
         finally:
             Bk.lane = prev
+
+    def _wgrad_window(self):
+        """opens a trunk block's backward: True where its weight-gradient launches go to the asynchronous lane (not inside a head's
+        lane).  The block is number `_bwd_seq` then; the launches read two alternating sets of transients (by the number's parity), so
+        the block waits for the asynchronous launches of block t-2 only"""
+        side = self.async_wgrad and self.bwd.lane == 0
+        if side:
+            self._bwd_seq += 1
+            self.bwd.join_async(f'blk{self._bwd_seq - 2}')
+        return side
+
+    def _wgrad_window_mark(self, side):
+        """after the block's last asynchronous launch: what block t+2 (and whoever rewrites a transient earlier) joins"""
+        if side:
+            self.bwd.async_mark(f'blk{self._bwd_seq}')
 
     def tmp(self, tag, shape, dtype=None):
         """transient buffer shared by every call site with the same (tag, shape, dtype) -- stream order makes it safe"""

@@ -5,15 +5,13 @@ SE-Bottleneck, GroupConvMlp, the whole GA head); the trunk is restated here from
   deep stem :463-477 ........ NCHW fp32 -> NHWC8 pack, three 3x3 convs as gather GEMMs (s2, s1, s2), LayerNorm+GELU fused
   CSWinBlock :191-212 ....... LN1 (affine folded into qkv) -> qkv GEMM -> stripe attention + LePE (one kernel for both
                               branches, windows addressed in place) -> proj GEMM (+DropPath, +residual) -> LN2 (folded)
-                              -> fc1+GELU(+GELU') -> fc2 (+DropPath, +residual);  GroupConvMlp when mlp_groups > 1
+                              -> fc1+GELU(+GELU') -> fc2 (+DropPath, +residual);  GroupConvMlp when mlp_groups > 1:
+                              engine_blocks.TransformerBlocks with cswin_block's facts (StripeAttention)
   Merge_Block :253-268 ...... 3x3 s2 gather GEMM (+bias) -> LayerNorm; data gradient as a transposed-conv GEMM
   aggregation :666-669 ...... avg-pool / taps / bilinear x2 into one concat buffer (ga_pool_concat)
   stage5 :531-542 ........... Merge_Block_LCF (1x1) + CSWinBlock, or the SE-Bottleneck
   heads :677-692 ............ grouped (g=8) gram_contraction + BN -> CSWinBlock(192, 6 heads) -> Gram -> grouped embed + BN
                               -> class attention (q/k/v width C/4) -> fc
-
-Saved for backward per CSWinBlock: xn1 (LN1 output without affine), rstd1, qkv, the attention output, xn2, rstd2,
-a = gelu(h), g = gelu'(h), the block output.
 """
 import os
 
@@ -22,7 +20,8 @@ import torch
 from . import ops
 from .engine import GAHeads
 from .engine_base import EngineBase, pad8
-from .ops import A_CONV3, A_CONV3S2, A_NEIGH2, ACT_GELU, C_UNPATCH2
+from .engine_blocks import BlockSpec, StripeAttention, TransformerBlocks
+from .ops import A_CONV3, A_CONV3S2, A_NEIGH2, C_UNPATCH2
 
 
 def tap_after(nblocks, naggre):
@@ -35,7 +34,13 @@ def tap_after(nblocks, naggre):
     return taps
 
 
-class CSWinEngine(GAHeads, EngineBase):
+def cswin_block(mod):
+    """ga_cswin.py:191-212 -- the facts of CSWinBlock `mod` (its parameter holder: geometry) for TransformerBlocks"""
+    return BlockSpec(C=mod.dim, heads=mod.num_heads, ntok=mod.reso * mod.reso, eps=1e-5, qkv='qkv.', proj='proj.',
+                     mlp_groups=mod.mlp_groups, attn=StripeAttention(mod))
+
+
+class CSWinEngine(TransformerBlocks, GAHeads, EngineBase):
     # ------------------------------------------------------------------------------------------
     def _drop_path_rates(self):
         """ga_cswin.py:486 (linspace over the 4 trunk stages), :538,571 (stage5 and gram layers: dpr[-1]), :541 (Bottleneck:
@@ -56,176 +61,6 @@ class CSWinEngine(GAHeads, EngineBase):
             out[f'gram_layer.{k}.1.#1'] = out[f'gram_layer.{k}.1.#2'] = dpr[-1]
             out[f'ga.{k}.'] = 0.0
         return out
-
-    # ------------------------------------------------------------------------------------------
-    # CSWinBlock
-    # ------------------------------------------------------------------------------------------
-    def _cs_block_fwd(self, pre, x, mod):
-        """x [B*reso*reso, C] -> block output (same shape); mod = the block's parameter holder (geometry).  Inside a forward chain
-        (EngineBase._chains: the trunk recorded once per batch part, each part on its own lane) the launches cover the chain's rows of
-        the same full-batch buffers; weight preparation and the saved state are recorded by the first pass only"""
-        F, dt, B, P, T = self.fwd, self.dt, self.B, self.P, self.training
-        C, reso, heads, mg = mod.dim, mod.reso, mod.num_heads, mod.mlp_groups
-        HW = reso * reso
-        M = B * HW
-        assert C % 8 == 0
-        (lane, r0, r1, b0, b1), = self._fsplits(HW)
-        first = pre not in self.blocks
-        assert mg == 1 or (r0 == 0 and r1 == M), 'grouped-MLP blocks are recorded for the whole batch'
-        if self._chain is not None:      # (outside a chain the caller's lane stands: the heads' gram_layer blocks)
-            F.lane = lane
-        dp1, dp2 = self.dp_scale.get(pre + '#1'), self.dp_scale.get(pre + '#2')
-        dp1c = dp1[b0:b1] if dp1 is not None else None
-        dp2c = dp2[b0:b1] if dp2 is not None else None
-        st = self.blocks.setdefault(pre, dict(x=x, mod=mod, M=M))
-        # --- attention branch
-        st['xn1'] = self.blk_act(pre + 'xn1', (M, C))
-        st['r1'] = self.blk_act(pre + 'r1', (M,), torch.float32)
-        F.layernorm_fwd(x[r0:r1], None, None, st['xn1'][r0:r1], None, st['r1'][r0:r1], r1 - r0, C, 1e-5, dt, label=pre + 'ln1')
-        Wqkv = self._w_plain(pre + 'qkv.weight', 3 * C, C, 1, 1, cs=P[pre + 'norm1.weight'])
-        bq = self.buf('w.' + pre + 'bqkv', (3 * C,), torch.float32)
-        if first:
-            self.prep.bias_fold(P[pre + 'qkv.weight'], P.get(pre + 'qkv.bias'), None, P[pre + 'norm1.bias'], bq, 3 * C, C)
-        st['qkv'] = self.blk_act(pre + 'qkv', (M, 3 * C))
-        F.gemm(st['xn1'][r0:r1], Wqkv, st['qkv'][r0:r1], r1 - r0, 3 * C, C, dt, bias=bq, label=pre + 'qkv')
-        st['att'] = self.blk_act(pre + 'att', (M, C))
-        lepe = [(P[pre + f'attns.{i}.get_v.weight'], P[pre + f'attns.{i}.get_v.bias']) for i in range(mod.branch_num)]
-        if first:      # the backward's descriptor: the whole batch
-            st['desc'] = F.cswin_desc(st['qkv'], st['att'], B, reso, C, heads, mod.stripes(), lepe, (C // heads) ** -0.5, dt)
-            self._lepe_ws_elems = max(self._lepe_ws_elems, ops.cswin_attn_bwd_workspace(st['desc']) // 4)
-        dfw = st['desc'] if (r0 == 0 and r1 == M) else F.cswin_desc(st['qkv'][r0:r1], st['att'][r0:r1], b1 - b0, reso, C, heads,
-                                                                       mod.stripes(), lepe, (C // heads) ** -0.5, dt)
-        F.cswin_attn_fwd(dfw, label=pre + 'attn')
-        Wp = self._w_plain(pre + 'proj.weight', C, C, 1, 1)
-        # x1 is re-read by the affine LayerNorm backward of the grouped-MLP form only
-        x1 = st['x1'] = self.buf(pre + 'x1', (M, C)) if (mg > 1 and T) else self.tmp('x1', (M, C))
-        F.gemm(st['att'][r0:r1], Wp, x1[r0:r1], r1 - r0, C, C, dt, bias=P[pre + 'proj.bias'], rowscale=dp1c, rows_per_scale=HW,
-               R=x[r0:r1], ldr=C, label=pre + 'proj')
-        # --- MLP branch
-        y = st['y'] = self.buf(pre + 'y', (M, C))
-        if mg == 1:
-            st['xn2'] = self.blk_act(pre + 'xn2', (M, C))
-            st['r2'] = self.blk_act(pre + 'r2', (M,), torch.float32)
-            F.layernorm_fwd(x1[r0:r1], None, None, st['xn2'][r0:r1], None, st['r2'][r0:r1], r1 - r0, C, 1e-5, dt, label=pre + 'ln2')
-            W1 = self._w_plain(pre + 'mlp.fc1.weight', 4 * C, C, 1, 1, cs=P[pre + 'norm2.weight'])
-            b1e = self.buf('w.' + pre + 'b1e', (4 * C,), torch.float32)
-            if first:
-                self.prep.bias_fold(P[pre + 'mlp.fc1.weight'], P[pre + 'mlp.fc1.bias'], None, P[pre + 'norm2.bias'], b1e, 4 * C, C)
-            st['a'] = self.blk_act(pre + 'a', (M, 4 * C))
-            st['g'] = self.buf(pre + 'g', (M, 4 * C)) if T else None
-            F.gemm(st['xn2'][r0:r1], W1, st['a'][r0:r1], r1 - r0, 4 * C, C, dt, bias=b1e, act=ACT_GELU,
-                   C2=st['g'][r0:r1] if T else None, c2_mode=2 if T else 0, label=pre + 'fc1')
-            W2 = self._w_plain(pre + 'mlp.fc2.weight', C, 4 * C, 1, 1)
-            F.gemm(st['a'][r0:r1], W2, y[r0:r1], r1 - r0, C, 4 * C, dt, bias=P[pre + 'mlp.fc2.bias'], rowscale=dp2c, rows_per_scale=HW,
-                   R=x1[r0:r1], ldr=C, label=pre + 'fc2')
-        else:
-            st['t'] = self.blk_act(pre + 't', (M, C))
-            st['m2'] = self.blk_act(pre + 'm2', (M,), torch.float32)
-            st['r2'] = self.blk_act(pre + 'r2', (M,), torch.float32)
-            F.layernorm_fwd(x1, P[pre + 'norm2.weight'], P[pre + 'norm2.bias'], st['t'], st['m2'], st['r2'], M, C, 1e-5, dt,
-                            label=pre + 'ln2')
-            st['mlp'] = self._gmlp_fwd(pre + 'mlp.', st['t'], M, C, mg, y, x1, dp2, HW)
-        return y
-
-    def _cs_block_bwd(self, pre, dy, dx, next_pre=None):
-        """dy: gradient wrt the block output; writes dx (a different buffer) = gradient wrt the block input"""
-        Bk, dt, B, P, W = self.bwd, self.dt, self.B, self.P, self.W
-        st = self.blocks[pre]
-        mod, M = st['mod'], st['M']
-        C, reso, mg = mod.dim, mod.reso, mod.mlp_groups
-        HW = reso * reso
-        dp1, dp2 = self.dp_scale.get(pre + '#1'), self.dp_scale.get(pre + '#2')
-        # trunk blocks: the weight-gradient launches go to the plan's asynchronous lane (nothing on the dgrad chain reads their
-        # results); two sets of the transients they read + three rotating dx buffers (caller), so this block only waits for the
-        # asynchronous launches of the block before the previous one (same scheme as ConvNeXtTrunk._block_bwd)
-        side = self.async_wgrad and Bk.lane == 0
-        par = ''
-        if side:
-            self._bwd_seq += 1
-            par = str(self._bwd_seq & 1)
-            Bk.join_async(f'blk{self._bwd_seq - 2}')
-        dyz = dy
-        if dp2 is not None:
-            dyz = self._pre_dyz.pop(pre, None)           # written by the LayerNorm backward of the block before (backward order)
-            if dyz is None:
-                dyz = self.tmp('dyz' + par, (M, C))
-                Bk.rowscale(dy, dp2, dyz, M * C, HW * C, dt, label=pre + 'dp2')
-        dx1 = self.tmp('dx1' + par, (M, C))
-        dx1z = dx1
-        fuse1 = dp1 is not None and self.fuse_dp and mg == 1
-        if fuse1:
-            dx1z = self.tmp('dx1z' + par, (M, C))
-        if mg == 1:
-            with self._wlane():
-                Bk.wgrad(dyz, st['a'], self.grad(pre + 'mlp.fc2.weight'), M, C, 4 * C, dt, dbias=self.grad(pre + 'mlp.fc2.bias'),
-                         label=pre + 'wg2')
-            dh = self.tmp('dh' + par, (M, 4 * C))
-            gb1 = self.gbuf((4 * C,))
-            Bk.gemm(dyz, W[pre + 'mlp.fc2.weight.T'], dh, M, 4 * C, C, dt, ldb=pad8(C), H=st['g'], ldh=4 * C, h_is_deriv=True,
-                    colsum=gb1, label=pre + 'dg2')
-            G1 = self.gbuf((4 * C, C))
-            with self._wlane():
-                Bk.wgrad(dh, st['xn2'], G1, M, 4 * C, C, dt, label=pre + 'wg1')
-            gx = self.tmp('g', (M, C))
-            Bk.gemm(dh, W[pre + 'mlp.fc1.weight.T'], gx, M, C, 4 * C, dt, ldb=pad8(4 * C), label=pre + 'dg1')
-            if fuse1:       # the DropPath-scaled copy of dx1 rides on the LayerNorm backward that writes dx1
-                Bk.layernorm_bwd(gx, st['xn2'], None, st['r2'], None, dy, dx1, None, None, M, C, True, dt, label=pre + 'ln2b', dx2=dx1z,
-                                 scale2=dp1, rows_per_scale=HW)
-            else:
-                Bk.layernorm_bwd(gx, st['xn2'], None, st['r2'], None, dy, dx1, None, None, M, C, True, dt, label=pre + 'ln2b')
-            Bk.weight_unfold(G1, C, 4 * C, C, gb=gb1, W=P[pre + 'mlp.fc1.weight'], b=P[pre + 'mlp.fc1.bias'],
-                             cs=P[pre + 'norm2.weight'], v=P[pre + 'norm2.bias'], dW=self.grad(pre + 'mlp.fc1.weight'),
-                             db=self.grad(pre + 'mlp.fc1.bias'), d_cs=self.grad(pre + 'norm2.weight'),
-                             d_v=self.grad(pre + 'norm2.bias'), label=pre + 'unf1')
-        else:
-            dtk = self.tmp('dtk', (M, C))
-            self._gmlp_bwd(pre + 'mlp.', st['mlp'], dyz, st['t'], M, C, mg, dtk)
-            Bk.layernorm_bwd(dtk, st['x1'], st['m2'], st['r2'], P[pre + 'norm2.weight'], dy, dx1, self.grad(pre + 'norm2.weight'),
-                             self.grad(pre + 'norm2.bias'), M, C, False, dt, label=pre + 'ln2b')
-        # --- attention branch
-        if dp1 is not None and not fuse1:
-            dx1z = self.tmp('dx1z' + par, (M, C))
-            Bk.rowscale(dx1, dp1, dx1z, M * C, HW * C, dt, label=pre + 'dp1')
-        with self._wlane():
-            Bk.wgrad(dx1z, st['att'], self.grad(pre + 'proj.weight'), M, C, C, dt, dbias=self.grad(pre + 'proj.bias'),
-                     label=pre + 'proj.wg')
-        datt = self.tmp('datt' + par, (M, C))
-        Bk.gemm(dx1z, W[pre + 'proj.weight.T'], datt, M, C, C, dt, ldb=pad8(C), label=pre + 'proj.dg')
-        dqkv = self.tmp('dqkv' + par, (M, 3 * C))
-        lepe_grads = [(self.grad(pre + f'attns.{i}.get_v.weight'), self.grad(pre + f'attns.{i}.get_v.bias'))
-                      for i in range(mod.branch_num)]
-        need = ops.cswin_attn_bwd_workspace(st['desc'])
-        if need:    # the MFMA kernel leaves the LePE weight-gradient partials of its LDS tiles; the reduce follows in stream order
-            lws = self.tmp('lepe_ws', (self._lepe_ws_elems,), torch.float32)
-            assert need <= lws.numel() * 4
-            Bk.cswin_attn_bwd(st['desc'], datt, dqkv, lepe_ws=lws, label=pre + 'attnb')
-            Bk.cswin_lepe_wgrad_reduce(st['desc'], lws, lepe_grads, label=pre + 'lepe.red')
-        else:
-            Bk.cswin_attn_bwd(st['desc'], datt, dqkv, label=pre + 'attnb')
-            with self._wlane():
-                Bk.cswin_lepe_wgrad(st['desc'], datt, lepe_grads, label=pre + 'lepe.wg')
-        Gq, gbq = self.gbuf((3 * C, C)), self.gbuf((3 * C,))
-        with self._wlane():
-            Bk.wgrad(dqkv, st['xn1'], Gq, M, 3 * C, C, dt, dbias=gbq, label=pre + 'qkv.wg')
-        has_b = (pre + 'qkv.bias') in P
-        Bk.weight_unfold(Gq, C, 3 * C, C, gb=gbq, W=P[pre + 'qkv.weight'], b=P.get(pre + 'qkv.bias'), cs=P[pre + 'norm1.weight'],
-                         v=P[pre + 'norm1.bias'], dW=self.grad(pre + 'qkv.weight'), db=self.grad(pre + 'qkv.bias') if has_b else None,
-                         d_cs=self.grad(pre + 'norm1.weight'), d_v=self.grad(pre + 'norm1.bias'), label=pre + 'qkv.unf')
-        gq = self.tmp('g', (M, C))
-        Bk.gemm(dqkv, W[pre + 'qkv.weight.T'], gq, M, C, 3 * C, dt, ldb=pad8(3 * C), label=pre + 'qkv.dg')
-        ndp = self.dp_scale.get(next_pre + '#2') if next_pre is not None else None
-        if ndp is not None and self.fuse_dp:
-            npar = str((self._bwd_seq + 1) & 1) if side else ''
-            ndyz = self.tmp('dyz' + npar, (M, C))
-            if side:           # that buffer was block t-1's: its asynchronous weight gradients must be done before it is rewritten
-                Bk.join_async(f'blk{self._bwd_seq - 1}')
-            Bk.layernorm_bwd(gq, st['xn1'], None, st['r1'], None, dx1, dx, None, None, M, C, True, dt, label=pre + 'ln1b', dx2=ndyz,
-                             scale2=ndp, rows_per_scale=HW)
-            self._pre_dyz[next_pre] = ndyz
-        else:
-            Bk.layernorm_bwd(gq, st['xn1'], None, st['r1'], None, dx1, dx, None, None, M, C, True, dt, label=pre + 'ln1b')
-        if side:
-            Bk.async_mark(f'blk{self._bwd_seq}')
 
     # ------------------------------------------------------------------------------------------
     # 3x3 / stride-2 conv (+bias) -> LayerNorm   (Merge_Block; the last stem conv without bias)
@@ -328,7 +163,7 @@ class CSWinEngine(GAHeads, EngineBase):
                     x, self.merges[si] = self._conv3s2_ln_fwd(f'merge{si}.conv.', f'merge{si}.norm.', x, stages[si - 1][0].reso,
                                                               d[si - 1], d[si], bias=True)
                 for j, mod in enumerate(stages[si]):
-                    x = self._cs_block_fwd(f'stage{si + 1}.{j}.', x, mod)
+                    x = self._tblock_fwd(f'stage{si + 1}.{j}.', x, cswin_block(mod))
                     if si == 2 and (j + 1) in taps_at:
                         taps.append((x, j))
                 feats.append((x, stages[si][0].reso))
@@ -353,7 +188,7 @@ class CSWinEngine(GAHeads, EngineBase):
             F.layernorm_fwd(L['c'], P[lp + 'norm.weight'], P[lp + 'norm.bias'], t5, L['mean'], L['rstd'], M4, cur, 1e-5, dt,
                             label=lp + 'ln')
             L['t5'] = t5
-            x4 = self._cs_block_fwd('stage5.2.', t5, m.stage5[2])
+            x4 = self._tblock_fwd('stage5.2.', t5, cswin_block(m.stage5[2]))
         else:
             x4 = self._bottleneck_fwd(cat, M4, ctot, cur, pre='stage5.')
         # ---------------- heads ----------------
@@ -440,10 +275,10 @@ class CSWinEngine(GAHeads, EngineBase):
     # gram_layer[k] = CSWinBlock(gram_dim, 6 heads) at 14 x 14 (ga_cswin.py:564-574)
     def _gram_layer_fwd(self, h, k, Hc):
         h['blk'] = f'gram_layer.{k}.1.'
-        return self._cs_block_fwd(h['blk'], h['g0'], self.m.gram_layer[k][1])
+        return self._tblock_fwd(h['blk'], h['g0'], cswin_block(self.m.gram_layer[k][1]))
 
     def _gram_layer_bwd(self, h, dg1, dg0):
-        self._cs_block_bwd(h['blk'], dg1, dg0)
+        self._tblock_bwd(h['blk'], dg1, dg0)
 
     # ------------------------------------------------------------------------------------------
     # whole-network backward plan
@@ -458,7 +293,7 @@ class CSWinEngine(GAHeads, EngineBase):
             L = self.lcf
             lp = 'stage5.1.'
             dt5 = self.tmp('dt5', (M4, cur))
-            self._cs_block_bwd('stage5.2.', dx4, dt5)
+            self._tblock_bwd('stage5.2.', dx4, dt5)
             dc5 = self.tmp('dc5', (M4, cur))
             Bk.layernorm_bwd(dt5, L['c'], L['mean'], L['rstd'], P[lp + 'norm.weight'], None, dc5, self.grad(lp + 'norm.weight'),
                              self.grad(lp + 'norm.bias'), M4, cur, False, dt, label=lp + 'lnb')
@@ -489,7 +324,7 @@ class CSWinEngine(GAHeads, EngineBase):
                 turn += 1
                 # the next block of the chain takes dx unchanged as its dy unless a tap gradient is added in between
                 nxt = f'stage{si + 1}.{j - 1}.' if j > 0 and not (si == 2 and (j - 1) in d_taps) else None
-                self._cs_block_bwd(f'stage{si + 1}.{j}.', dy, dx, next_pre=nxt)
+                self._tblock_bwd(f'stage{si + 1}.{j}.', dy, dx, next_pre=nxt)
                 dy = dx
             if si > 0:
                 Hp = stages[si - 1][0].reso

@@ -4,7 +4,7 @@ MAPPiTEngine: that trunk feeding the MAP head (pool_type='map'; engine_map.MAPHe
   conv_embedding (:71-81, 16 x 16 / stride 8, overlapping) ... ga_patchify_strided + ga_gemm (bias in the epilogue)
   + pos_embed (:190-191, an NCHW parameter) ..................... transposed once per step to [HW][C]; ga_pos_add_fwd / _bwd
   Transformer stages (:23-55; rearrange to tokens, timm Blocks) .. token rows ARE the NHWC map: no rearrange; the ViT block of
-                                                                    engine_vit (LayerNorm folded into the next linear, ga_attn_*
+                                                                    engine_blocks (LayerNorm folded into the next linear, ga_attn_*
                                                                     with head_dim 48 on the zero-padded 64-wide MFMA tiles)
   conv_head_pooling (:58-68) ...................................... ga_dwpool_fwd / _bwd_data / _bwd_weight
   forward_features' list (:185-201) -> MAPHead (:133-144) ......... MultiScale at the level-2 map's size: the two 27 x 27 maps
@@ -18,11 +18,11 @@ import torch
 
 from . import ops  # noqa: F401
 from .engine_base import EngineBase
+from .engine_blocks import TransformerBlocks, timm_block
 from .engine_map import MAPHead
-from .engine_vit import ViTBlocks
 
 
-class PiTTrunk(ViTBlocks):
+class PiTTrunk(TransformerBlocks):
     """builder: conv_embedding + pos_embed and the three transformer stages with their pooling convolutions, forward and backward"""
 
     def _drop_path_rates(self):
@@ -71,9 +71,9 @@ class PiTTrunk(ViTBlocks):
             hw = w0
             for s_ in range(3):
                 C, Ntok = dims[s_], hw * hw
-                xin = x
+                xin, spec = x, timm_block(C, heads[s_], Ntok)
                 for j in range(depth[s_]):
-                    x = self._vit_block_fwd(f'transformers.{s_}.blocks.{j}.', x, B * Ntok, C, heads[s_], Ntok)
+                    x = self._tblock_fwd(f'transformers.{s_}.blocks.{j}.', x, spec)
                 feats.append((x, hw, C))
                 self.stage_io.append((xin, x, hw, C))
                 if s_ < 2:
@@ -104,8 +104,8 @@ class PiTTrunk(ViTBlocks):
             for j in range(depth[s] - 1, -1, -1):
                 cur = (cur + 1) % 3
                 dx = rot[cur][:M * C].view(M, C)
-                self._vit_block_bwd(f'transformers.{s}.blocks.{j}.', dy, dx, M, C, Ntok,
-                                    next_pre=f'transformers.{s}.blocks.{j - 1}.' if j > 0 else None)      # (stage seams add a feature seed)
+                self._tblock_bwd(f'transformers.{s}.blocks.{j}.', dy, dx,
+                                 next_pre=f'transformers.{s}.blocks.{j - 1}.' if j > 0 else None)      # (stage seams add a feature seed)
                 dy = dx
             if s > 0:
                 # conv_head_pooling backward; the stage below's output also fed MultiScale: its seed is added
