@@ -1,8 +1,8 @@
 """GAEngine: the launch plans of one GA_ConvNeXt = engine_base.EngineBase + the builders of this module:
 
   ConvNeXtTrunk ... stem + the four ConvNeXt stages, forward and backward (GA-ConvNeXt, MAP-ConvNeXt and the plain ConvNeXt);
-  GroupMlp ........ GroupConvMlp forward / backward and the zero-padded parameter copies of the odd-width variants (both heads);
-  GAHeads ......... aggregation into the concat buffer, SE-Bottleneck, the five GA heads (GA-ConvNeXt, GA-CSWin).
+  GAHeads ......... aggregation into the concat buffer, SE-Bottleneck, the five GA heads (GA-ConvNeXt, GA-CSWin), on the stacked
+                    products and the GroupConvMlp of engine_heads.HeadStacks.
 
 What is saved for backward per ConvNeXt block: xhat (LN output, no affine), rstd, h (pre-GELU hidden) and the
 block output of fc1 as a = gelu(h) and g = gelu'(h) (both written by the fc1 epilogue), and the block output.
@@ -16,6 +16,7 @@ import torch
 
 from . import ops
 from .engine_base import EngineBase, GAFunction, pad8  # noqa: F401  (GAFunction, pad8: this module's long-standing exports)
+from .engine_heads import HeadStacks, Stacked
 from .ops import (A_CONV3, A_PATCH2, A_STEM4_NCHW, ACT_GELU, ASYNC_LANE, C_UNPATCH2, GA_BF16)
 
 
@@ -327,187 +328,7 @@ class ConvNeXtTrunk:
         self.input_bwd_desc = self._last_desc(Bk)
 
 
-class GroupMlp:
-    """builder: GroupConvMlp (the GA heads' and the MAP head's MLP) and the zero-padded copies of parameters that the odd-width
-    variants run on.  `_init_group_mlp` comes first in the build of a family that uses it."""
-
-    def _init_group_mlp(self):
-        # zero-padded copies of parameters of the odd-width variants: name -> (padded buffer, how to copy); gradients: name -> arena buffer
-        self.ppad, self.pgrad = {}, {}
-        self.pad_gmlp = os.environ.get('GAEXT_PAD_GMLP', '1') != '0'    # odd-width grouped one-token layers on padded MFMA layouts
-
-    def _pw(self, name):
-        """master copy of a parameter: the zero-padded one where the layer runs on a padded layout"""
-        return self.ppad[name][0] if name in self.ppad else self.P[name]
-
-    def _pg(self, name):
-        """gradient buffer of a parameter (padded: a zeroed arena buffer, copied back by _unpad_all)"""
-        if name not in self.ppad:
-            return self.grad(name)
-        if name not in self.pgrad:
-            self.pgrad[name] = self.gbuf(tuple(self.ppad[name][0].shape))
-        return self.pgrad[name]
-
-    def _pad_groups(self, name, R, Cdim, RG, RGp, CG, CGp):
-        """register (once) the two-level group-padded copy of parameter `name` ([R][C] -> [R/RG*RGp][C/CG*CGp], ga_pad_groups_f32)"""
-        if name not in self.ppad:
-            buf = self.buf('pad.' + name, (R // RG * RGp, Cdim // CG * CGp), torch.float32, zero=True)
-            self.prep.pad_groups_f32(self.P[name], buf, R, Cdim, RG, RGp, CG, CGp, label='prep.pad.' + name)
-            self.ppad[name] = (buf, 'groups', (R, Cdim, RG, RGp, CG, CGp))
-        return self.ppad[name][0]
-
-    def _unpad_all(self):
-        """real part of every padded parameter gradient back into the parameter's gradient; call AFTER the flush of the heads'
-        deferred weight-unfold jobs (they write the padded gradients) and before the 'heads' mark (_seal(..., then=self._unpad_all))"""
-        for name, g in self.pgrad.items():
-            _, kind, a = self.ppad[name]
-            if kind == 'copy':
-                rows, cols, lds, ldd = a
-                self.bwd.pad_copy_f32(g, self.grad(name), rows, cols, ldd, lds, accumulate=True, label=name + '.unpad')
-            else:
-                self.bwd.pad_groups_f32(g, self.grad(name), *a, unpad=True, accumulate=True, label=name + '.unpad')
-
-    # ------------------------------------------------------------------------------------------
-    # GroupConvMlp (ga_convnext.py:190-222, ga_cswin.py:321-349): grouped fc1 -> GELU -> channel_shuffle -> grouped fc2
-    # on `rows` tokens.  The shuffle is folded into the ROW ORDER of fc1's effective weights: hidden index
-    # n = gi*gc + ci  <-  fc1 output channel ci*mg + gi; with Nv = gc / mg rows per "virtual group" the fc1 input group is
-    # constant inside one (= v % mg), so fc1 is a batched GEMM over mg*mg virtual groups and fc2 one over mg groups.
-    # ------------------------------------------------------------------------------------------
-    def _gmlp_fwd(self, pre, t, rows, C, mg, out, R, rowscale, rps, gamma_name=None, act='gelu', drop_mask=None, ratio=4):
-        """out = R + rowscale * gamma * fc2(shuffle(drop(act(fc1(t)))));  pre = '<block>.mlp.';  act 'gelu' (GA) or 'relu'
-        (MAP, map.py:467) with an optional dropout mask [rows, ratio * C] on the hidden layer (in the SHUFFLED channel order);
-        ratio: the hidden width over C (mlp_ratio; with mg = 1 the channel shuffle is the identity)"""
-        F, dt, P, T = self.fwd, self.dt, self.P, self.training
-        gamma = self._pw(gamma_name) if gamma_name else None
-        Hd = int(ratio * C)
-        gc_ = Hd // mg
-        Nv = gc_ // mg          # rows per virtual group (fc1 input group is constant inside one)
-        cin = C // mg
-        n_idx = torch.arange(Hd)
-        perm = ((n_idx % gc_) * mg + n_idx // gc_).to(torch.int32).to(self.dev)
-        if (Nv % 8 or cin % 8) and self.pad_gmlp and C % mg == 0:
-            # odd widths (688 / 4 = 172 channels per group) on the MFMA kernels: the layer runs as a GroupConvMlp of mg groups of
-            # cin_p = pad8(cin) channels on zero-padded copies of its five parameters (fc1 rows in groups of 4 cin -> 4 cin_p and
-            # columns cin -> cin_p; fc2 rows and columns in groups of cin -> cin_p; ga_pad_groups_f32) and group-padded copies of
-            # its input / residual; padded hidden and output channels are exact zeros (zero weights, zero biases), the real part
-            # of the output is compacted back and the real part of every padded gradient copied back after the backward pass
-            assert Hd == 4 * C, 'the padded odd-width layout is laid out for mlp_ratio 4'
-            cin_p = pad8(cin)
-            Cp = mg * cin_p
-            self._pad_groups(pre + 'fc1.weight', Hd, cin, 4 * cin, 4 * cin_p, cin, cin_p)
-            self._pad_groups(pre + 'fc1.bias', 1, Hd, 1, 1, 4 * cin, 4 * cin_p)
-            self._pad_groups(pre + 'fc2.weight', C, gc_, cin, cin_p, cin, cin_p)
-            self._pad_groups(pre + 'fc2.bias', 1, C, 1, 1, cin, cin_p)
-            if gamma_name:
-                self._pad_groups(gamma_name, 1, C, 1, 1, cin, cin_p)
-            # (persistent zero-initialised buffers: the pad columns are never written)
-            tp = self.buf(pre + 't.pad', (rows, Cp), zero=True)
-            F.pad_copy(t, tp, rows * mg, cin, cin, cin_p, dt, label=pre + 't.pad')
-            Rp = None
-            if R is not None:
-                Rp = self.buf(pre + 'R.pad', (rows, Cp), zero=True)
-                F.pad_copy(R, Rp, rows * mg, cin, cin, cin_p, dt, label=pre + 'R.pad')
-            outp = self.tmp('gmlp.out.pad', (rows, Cp))
-            st = self._gmlp_fwd(pre, tp, rows, Cp, mg, outp, Rp, rowscale, rps, gamma_name=gamma_name, act=act, drop_mask=drop_mask)
-            F.pad_copy(outp, out, rows * mg, cin, cin_p, cin, dt, label=pre + 'out.unpad')
-            st['pad'] = dict(tp=tp, Cp=Cp, cin=cin, cin_p=cin_p)
-            return st
-        if Nv % 8 or cin % 8:
-            # the same layers on the alignment-free kernels (GAEXT_PAD_GMLP=0), fp32 master weights,
-            # the channel_shuffle as a column map of fc2's input (hidden kept in the ORIGINAL channel order, pre-activation saved)
-            assert act == 'gelu' and drop_mask is None and rows <= 4096, (pre, C, mg, rows)
-            st = dict(naive=True, Hd=Hd, hpre=self.act(pre + 'hpre', (rows, Hd)), am=self.act(pre + 'am', (rows, Hd)),
-                      yraw=self.act(pre + 'yraw', (rows, C)) if T else None)
-            st['d1'] = F.small_linear_desc(t, P[pre + 'fc1.weight'], st['hpre'], rows, mg, gc_, cin, dt, lda=C, a_gstride=cin, ldy=Hd,
-                                           bias=P[pre + 'fc1.bias'])
-            F.small_linear_fwd(st['d1'], label=pre + 'fc1')
-            F.gelu_fwd(st['hpre'], st['am'], rows * Hd, dt, label=pre + 'gelu')
-            kw = dict(bias=P[pre + 'fc2.bias'], a_perm=perm, col_scale=gamma, Yraw=st['yraw'])
-            d2 = F.small_linear_desc(st['am'], P[pre + 'fc2.weight'], out, rows, mg, cin, gc_, dt, lda=Hd, a_gstride=gc_, ldy=C,
-                                     rowscale=rowscale, rows_per_scale=rps, R=R, ldr=C, **kw)
-            F.small_linear_fwd(d2, label=pre + 'fc2')
-            # the backward sees a gradient that already carries the DropPath scale: same layer without the row scale
-            st['d2b'] = F.small_linear_desc(st['am'], P[pre + 'fc2.weight'], out, rows, mg, cin, gc_, dt, lda=Hd, a_gstride=gc_, ldy=C, **kw)
-            return st
-        assert gc_ % mg == 0, (pre, C, mg)
-        Wm1 = self._w_plain(pre + 'fc1.weight', Nv, cin, 1, 1, groups=mg * mg, row_perm=perm, src=self._pw(pre + 'fc1.weight'))
-        bm1 = self.buf('w.' + pre + 'bm1', (Hd,), torch.float32)
-        self.prep.bias_fold(None, self._pw(pre + 'fc1.bias'), None, None, bm1, Hd, cin, row_perm=perm)
-        st = dict(perm=perm, Hd=Hd, gc=gc_, Nv=Nv, cin=cin)
-        st['am'] = self.act(pre + 'am', (rows, Hd))                      # gelu(hidden), shuffled order
-        st['gm'] = self.act(pre + 'gm', (rows, Hd)) if T else None       # gelu'(hidden)
-        if act == 'gelu':
-            assert drop_mask is None
-            F.gemm(t, Wm1, st['am'], rows, Nv, cin, dt, lda=C, batch=mg * mg, strideA=cin, a_batch_mod=mg,
-                   strideB=Nv * pad8(cin), ldb=pad8(cin), ldc=Hd, strideC=Nv, bias=bm1, strideBias=Nv, act=ACT_GELU,
-                   C2=st['gm'], c2_mode=2 if T else 0, label=pre + 'fc1')
-        else:   # ReLU: its derivative (times the dropout mask) is a small pass of its own; the GEMM epilogue stays generic
-            two = T or drop_mask is not None
-            raw = self.tmp('am_raw', (rows, Hd)) if two else st['am']
-            F.gemm(t, Wm1, raw, rows, Nv, cin, dt, lda=C, batch=mg * mg, strideA=cin, a_batch_mod=mg,
-                   strideB=Nv * pad8(cin), ldb=pad8(cin), ldc=Hd, strideC=Nv, bias=bm1, strideBias=Nv, act=ops.ACT_RELU,
-                   label=pre + 'fc1')
-            if two:
-                F.relu_drop(raw, drop_mask, st['am'], st['gm'], rows * Hd, dt, label=pre + 'relu')
-        Wm2 = self._w_plain(pre + 'fc2.weight', cin, gc_, 1, 1, groups=mg, rs=gamma, src=self._pw(pre + 'fc2.weight'))
-        bm2 = self.buf('w.' + pre + 'bm2', (C,), torch.float32)
-        self.prep.bias_fold(None, self._pw(pre + 'fc2.bias'), gamma, None, bm2, C, gc_)
-        F.gemm(st['am'], Wm2, out, rows, cin, gc_, dt, lda=Hd, batch=mg, strideA=gc_, strideB=cin * pad8(gc_),
-               ldb=pad8(gc_), ldc=C, strideC=cin, bias=bm2, strideBias=cin, rowscale=rowscale,
-               rows_per_scale=rps, R=R, ldr=C, strideR=cin, label=pre + 'fc2')
-        return st
-
-    def _gmlp_bwd(self, pre, st, dmz, t, rows, C, mg, dtk, gamma_name=None):
-        """dmz: gradient wrt the MLP branch output (DropPath scale already applied) -> dtk = gradient wrt the input t"""
-        Bk, dt, P, W = self.bwd, self.dt, self.P, self.W
-        gamma = self._pw(gamma_name) if gamma_name else None
-        if 'pad' in st:       # the padded layer (see _gmlp_fwd): group-padded gradient in, real part of the input gradient out
-            pd = st.pop('pad')
-            cin, cin_p, Cp = pd['cin'], pd['cin_p'], pd['Cp']
-            dmzp = self.buf(pre + 'dmz.pad', (rows, Cp), zero=True)
-            Bk.pad_copy(dmz, dmzp, rows * mg, cin, cin, cin_p, dt, label=pre + 'dmz.pad')
-            dtkp = self.tmp('gmlp.dt.pad', (rows, Cp))
-            self._gmlp_bwd(pre, st, dmzp, pd['tp'], rows, Cp, mg, dtkp, gamma_name=gamma_name)
-            Bk.pad_copy(dtkp, dtk, rows * mg, cin, cin_p, cin, dt, label=pre + 'dt.unpad')
-            st['pad'] = pd
-            return
-        if st.get('naive'):
-            Hd = st['Hd']
-            dam, dh = self.tmp('dam', (rows, Hd)), self.tmp('dhm', (rows, Hd))
-            Bk.small_linear_bwd(st['d2b'], dmz, dA=dam, dW=self.grad(pre + 'fc2.weight'), dbias=self.grad(pre + 'fc2.bias'),
-                                dcol_scale=self.grad(gamma_name) if gamma_name else None, label=pre + 'fc2.bwd')
-            Bk.gelu_bwd(dam, st['hpre'], dh, rows * Hd, dt, label=pre + 'geluB')
-            Bk.small_linear_bwd(st['d1'], dh, dA=dtk, dW=self.grad(pre + 'fc1.weight'), dbias=self.grad(pre + 'fc1.bias'),
-                                label=pre + 'fc1.bwd')
-            return
-        Hd, gc_, Nv, cin = st['Hd'], st['gc'], st['Nv'], st['cin']
-        # fc2 (mg groups)
-        Gm2, gbm2 = self.gbuf((C, gc_)), self.gbuf((C,))
-        Bk.wgrad(dmz, st['am'], Gm2, rows, cin, gc_, dt, ldy=C, ldx=Hd, ldw=gc_, batch=mg, strideY=cin, strideX=gc_,
-                 strideW=cin * gc_, dbias=gbm2, strideDbias=cin, label=pre + 'fc2.wg')
-        Bk.weight_unfold(Gm2, gc_, C, gc_, gb=gbm2, W=self._pw(pre + 'fc2.weight'), b=self._pw(pre + 'fc2.bias'),
-                         rs=gamma, dW=self._pg(pre + 'fc2.weight'), db=self._pg(pre + 'fc2.bias'),
-                         d_rs=self._pg(gamma_name) if gamma_name else None, label=pre + 'fc2.unf')
-        dhm = self.tmp('dhm', (rows, Hd))
-        gbm1 = self.gbuf((Hd,))
-        Bk.gemm(dmz, W[pre + 'fc2.weight.T'], dhm, rows, gc_, cin, dt, lda=C, batch=mg, strideA=cin,
-                strideB=gc_ * pad8(cin), ldb=pad8(cin), ldc=Hd, strideC=gc_, H=st['gm'], ldh=Hd, strideH=gc_, h_is_deriv=True,
-                colsum=gbm1, strideCol=gc_, label=pre + 'fc2.dg')
-        # fc1 (mg*mg virtual groups)
-        Gm1 = self.gbuf((Hd, cin))
-        Bk.wgrad(dhm, t, Gm1, rows, Nv, cin, dt, ldy=Hd, ldx=C, ldw=cin, batch=mg * mg, strideY=Nv, strideX=cin,
-                 x_batch_mod=mg, strideW=Nv * cin, label=pre + 'fc1.wg')
-        Bk.weight_unfold(Gm1, cin, Hd, cin, gb=gbm1, W=self._pw(pre + 'fc1.weight'), b=self._pw(pre + 'fc1.bias'),
-                         row_perm=st['perm'], dW=self._pg(pre + 'fc1.weight'), db=self._pg(pre + 'fc1.bias'),
-                         label=pre + 'fc1.unf')
-        Wm1T = W[pre + 'fc1.weight.T']            # [mg*mg][cin][pad8(Nv)]
-        for gi in range(mg):
-            Bk.gemm(dhm[:, gi * gc_:], Wm1T[gi * mg * cin:], dtk, rows, cin, Nv, dt, lda=Hd, batch=mg, strideA=Nv,
-                    strideB=cin * pad8(Nv), ldb=pad8(Nv), ldc=C, strideC=cin, R=dtk if gi > 0 else None, ldr=C,
-                    strideR=cin, label=pre + f'fc1.dg{gi}')
-
-
-class GAHeads(GroupMlp):
+class GAHeads(HeadStacks):
     """builder: what follows the trunk of a GA model -- the aggregation of the stage outputs and taps into one concat buffer, the
     SE-Bottleneck and the five GA heads.  The family supplies `_gram_layer_fwd` / `_gram_layer_bwd` (gram_layer[k] is a block of its
     own trunk) and sets `self.cout`, the width of the map the heads read."""
@@ -690,16 +511,12 @@ class GAHeads(GroupMlp):
 
     def _build_heads(self, x4, M4, Hc):
         """the five GA heads on the stage-4 / stage-5 map x4 [M4, cout] (ga_convnext.py:491-504, ga_cswin.py:677-692)"""
-        cfg, B, T, F, dt = self.cfg, self.B, self.training, self.fwd, self.dt
+        cfg, B, F = self.cfg, self.B, self.fwd
         cout = self.cout
         NC, K = cfg['num_classes'], cfg['branches']
         assert NC % 8 == 0, 'num_classes must be a multiple of 8 (pad the classifier)'
         self.logits = self.buf('logits', (K, B, NC), torch.float32)
         self.heads = []
-        # LayerScaleBlockClassAttn.norm1 acts row-wise on cat(x_cls, tokens) (ga_convnext.py:244-246): the normalised
-        # image tokens are the SAME for all heads (only the affine part differs, and that is folded into each head's
-        # k | v | q weights like the ConvNeXt block's LayerNorm into fc1).  One LayerNorm over the tokens instead of five
-        # over the concatenation, no concatenated copy, one backward LayerNorm over the summed gradient.
         E_, nh_ = cfg['dim_embed'], cfg['num_heads']
         # ga_class_attn_*2 wants head widths that are multiples of 8 and E <= 512.  Odd head widths (688 / 976 variants:
         # dim_embed 168 / 240 = 8 heads of 21 / 30) run hd_p = pad8(hd) wide on zero-padded COPIES of the q / k / v rows and the
@@ -709,11 +526,11 @@ class GAHeads(GroupMlp):
         self.hd_p = pad8(hd_)
         self.Ea = nh_ * self.hd_p
         self.shared_tok = E_ % nh_ == 0 and self.Ea <= 512
+        for k in range(K):      # k and v projections are one stacked [2E, cout] matrix
+            self._kv_adjacent(f'ga.{k}.attn.k', f'ga.{k}.attn.v')
         if self.shared_tok and self.Ea != E_:
             for k in range(K):
                 pre = f'ga.{k}.attn.'
-                pk, pv = self.P[pre + 'k.weight'], self.P[pre + 'v.weight']
-                assert pv.data_ptr() == pk.data_ptr() + pk.numel() * 4, 'k/v weights must be adjacent in the flat buffer'
                 # (name, padded shape, rows, cols, source row pitch, padded row pitch)
                 spec = (('k.weight', (2 * self.Ea, cout), 2 * nh_, hd_ * cout, hd_ * cout, self.hd_p * cout),
                         ('q.weight', (self.Ea, cout), nh_, hd_ * cout, hd_ * cout, self.hd_p * cout),
@@ -723,70 +540,28 @@ class GAHeads(GroupMlp):
                     self.prep.pad_copy_f32(self.P[pre + name], buf, rows, cols, lds, ldd, label='prep.pad.' + pre + name)
                     self.ppad[pre + name] = (buf, 'copy', (rows, cols, lds, ldd))
         if self.shared_tok:
-            self.tok = dict(xn=self.act('ga.tok.xn', (M4, cout)), rstd=self.act('ga.tok.rstd', (M4,), torch.float32))
-            F.layernorm_fwd(x4, None, None, self.tok['xn'], None, self.tok['rstd'], M4, cout, 1e-5, dt, label='ga.tok.ln')
-            # the k | v rows of the image tokens of ALL heads from one GEMM over the shared tokens: the heads' effective
-            # (norm1-folded) k|v weights are stacked along N; head k reads / writes the column slice [k*2E, (k+1)*2E)
-            E2 = 2 * self.Ea
-            tk = self.tok
-            tk['E2'], tk['ld'] = E2, K * E2
-            tk['W'] = self.buf('w.ga.kv_all', (K * E2, cout))
-            tk['WT'] = self.buf('wT.ga.kv_all', (cout, K * E2)) if T else None
-            tk['b'] = self.buf('w.ga.bkv_all', (K * E2,), torch.float32)
-            P = self.P
-            for k in range(K):
-                pre = f'ga.{k}.'
-                pk, pv = P[pre + 'attn.k.weight'], P[pre + 'attn.v.weight']
-                assert pv.data_ptr() == pk.data_ptr() + pk.numel() * 4, 'k/v weights must be adjacent in the flat buffer'
-                pk = self._pw(pre + 'attn.k.weight')
-                self.prep.weight_prep(pk, 1, E2, cout, 1, 1, dt, out=tk['W'][k * E2:], ldo=cout,
-                                      outT=tk['WT'][:, k * E2:] if T else None, ldt=K * E2 if T else 0,
-                                      cs=P[pre + 'norm1.weight'], t_cols=E2, label='prep.' + pre + 'kv')
-                self.prep.bias_fold(pk, None, None, P[pre + 'norm1.bias'], tk['b'][k * E2:], E2, cout)
-            tk['kv'] = self.act('ga.kv_all', (M4, K * E2))
-            F.gemm(tk['xn'], tk['W'], tk['kv'], M4, K * E2, cout, dt, bias=tk['b'], label='ga.kv_all')
+            # LayerScaleBlockClassAttn.norm1 on cat(x_cls, tokens) (ga_convnext.py:244-246) as the shared-token k|v stack: its affine
+            # part is folded into each head's k | v (and q) weights
+            self.tok = self._tok_stack_fwd('ga', x4, M4, cout, 2 * self.Ea, 1e-5,
+                                           [Stacked(f'ga.{k}.attn.k.weight', norm=f'ga.{k}.norm1.', pre=f'ga.{k}.') for k in range(K)])
         self._contract_all_fwd(x4, M4)
         # classifiers: inputs of the five heads in one [K][B][cout] buffer, weights stacked -> one batched GEMM
-        fa = self.fc_all = dict(x=self.act('fc.all.x', (K, B, cout)))
-        ldn = pad8(NC)
-        fa['W'] = self.buf('w.fc.all', (K, NC, cout))
-        fa['WT'] = self.buf('wT.fc.all', (K, cout, ldn)) if T else None
-        fa['b'] = self.buf('w.fc.ball', (K, NC), torch.float32)
-        for k in range(K):
-            self.prep.weight_prep(self.P[f'fc.{k}.weight'], 1, NC, cout, 1, 1, dt, out=fa['W'][k], ldo=cout,
-                                  outT=fa['WT'][k] if T else None, ldt=ldn if T else 0, label=f'prep.fc.{k}')
-            self.prep.bias_fold(None, self.P[f'fc.{k}.bias'], None, None, fa['b'][k], NC, cout)
-        # the heads are independent chains of mostly small launches: with GAEXT_HEAD_STREAMS=n > 1 head k runs on side
-        # stream k % n (between a fork / join of the plan) with its own transient buffers
+        self.fc_all = self._fc_stack('all', K, cout, [Stacked(f'fc.{k}.weight', f'fc.{k}.bias', prep=f'prep.fc.{k}') for k in range(K)])
+        # with GAEXT_HEAD_STREAMS=n > 1 head k runs on side stream k % n (between a fork / join of the plan)
         self.head_lanes = int(os.environ.get('GAEXT_HEAD_STREAMS', '5')) if self.shared_tok else 1
-        for k in range(K):
-            if self.head_lanes > 1:
-                F.lane, self.tmp_prefix = 1 + k % self.head_lanes, f'h{k}.'
+        for k in self._each_head(F, K):
             self.heads.append(self._head_fwd(k, x4, M4, cout, Hc))
-        F.lane, self.tmp_prefix = 0, ''
-        F.gemm(fa['x'], fa['W'], self.logits, B, NC, cout, dt, batch=K, strideA=B * cout, strideB=NC * cout, strideC=B * NC,
-               bias=fa['b'], strideBias=NC, c_f32=True, label='fc.all')
+        self._fc_stack_fwd(self.fc_all, self.logits)
+
+    def _contraction_heads(self):
+        """gram_contraction[k] = conv1x1 + BatchNorm, as the conv stack's data"""
+        return [Stacked(f'gram_contraction.{k}.0.weight', f'gram_contraction.{k}.0.bias', norm=f'gram_contraction.{k}.1.',
+                        pre=f'gram_contraction.{k}.', prep=f'prep.gram_contraction.{k}.w', bufs=f'gram_contraction.{k}.1.')
+                for k in range(self.cfg['branches'])]
 
     def _contract_all_fwd(self, x4, M4):
-        cfg, T, F, dt, cout = self.cfg, self.training, self.fwd, self.dt, self.cout
-        K = cfg['branches']
-        # gram_contraction (conv1x1 768 -> 192 + BN) of the five heads reads the same x4: ONE GEMM with the five weight
-        # matrices stacked along N; head k owns the column slice [k*g, (k+1)*g) of its output / statistics
-        g_ = cfg['gram_dim']
-        gc = self.gcon = dict(ld=K * g_)
-        gc['W'] = self.buf('w.gram_contraction.all', (K * g_, cout))
-        gc['WT'] = self.buf('wT.gram_contraction.all', (cout, K * g_)) if T else None
-        gc['b'] = self.buf('w.gram_contraction.ball', (K * g_,), torch.float32)
-        gc['s'], gc['q'] = self._bn_pool(K * g_), self._bn_pool(K * g_)
-        for k in range(K):
-            pre = f'gram_contraction.{k}.'
-            self.prep.weight_prep(self.P[pre + '0.weight'], 1, g_, cout, 1, 1, dt, out=gc['W'][k * g_:], ldo=cout,
-                                  outT=gc['WT'][:, k * g_:] if T else None, ldt=K * g_ if T else 0, t_cols=g_,
-                                  label='prep.' + pre + 'w')
-            self.prep.bias_fold(None, self.P[pre + '0.bias'], None, None, gc['b'][k * g_:], g_, cout)
-        gc['out'] = self.act('gram_contraction.all.out', (M4, K * g_))
-        F.gemm(x4, gc['W'], gc['out'], M4, K * g_, cout, dt, bias=gc['b'], colsum=gc['s'] if T else None,
-               colsumsq=gc['q'] if T else None, label='gram_contraction.all')
+        """gram_contraction (conv1x1 768 -> 192 + BN) of the five heads"""
+        self.gcon = self._conv_stack_fwd('gram_contraction', x4, M4, self.cout, self.cfg['gram_dim'], self._contraction_heads())
 
     def _head_supported(self):
         cfg, cout = self.cfg, self.cout
@@ -814,25 +589,13 @@ class GAHeads(GroupMlp):
                 f"{8 * cfg['mlp_groups']} (per-group channel counts that are multiples of 8); the *_768 / *_1024 variants "
                 f"qualify, *_688 / *_976 need padded group layouts (not built)")
         h = dict(k=k)
-        self._head_contract_fwd(h, k, M4)
+        # gram_contraction[k]'s BatchNorm on this head's column slice of the stacked conv output -> h['g0'] [M4, gram_dim]
+        gcn = self.gcon
+        h['gc'] = gcn['out'][:, k * gcn['n']:]                      # [M4, g] view, row stride gcn['ld']
+        h['bn_gc'], h['g0'] = self._conv_stack_bn_fwd(gcn, k, h['gc'], f'gram_contraction.{k}.g0')
         h['g1'] = self._gram_layer_fwd(h, k, Hc)
         self._head_tail_fwd(h, k, x4, M4, cout, Hc)
         return h
-
-    def _head_contract_fwd(self, h, k, M4):
-        """gram_contraction[k]'s BatchNorm on this head's column slice of the stacked conv output -> h['g0'] [M4, gram_dim]"""
-        F, dt, g = self.fwd, self.dt, self.cfg['gram_dim']
-        # --- gram_contraction: the conv output / batch sums are column slices of the stacked GEMM; BN per head
-        pre = f'gram_contraction.{k}.'
-        gcn = self.gcon
-        h['gc'] = gcn['out'][:, k * g:]                      # [M4, g] view, row stride gcn['ld']
-        bn = dict(s=gcn['s'][k * g:(k + 1) * g], q=gcn['q'][k * g:(k + 1) * g],
-                  mean=self.buf(pre + '1.bmean', (g,), torch.float32), rstd=self.buf(pre + '1.brstd', (g,), torch.float32),
-                  scale=self.buf(pre + '1.scale', (g,), torch.float32), shift=self.buf(pre + '1.shift', (g,), torch.float32))
-        h['bn_gc'] = bn
-        self._bn_finalize(pre + '1.', bn, M4, g)
-        h['g0'] = self.buf(pre + 'g0', (M4, g))
-        F.affine_act(h['gc'], bn['scale'], bn['shift'], None, h['g0'], M4, g, False, dt, ldx=gcn['ld'], label=pre + 'bn')
 
     def _head_tail_fwd(self, h, k, x4, M4, cout, Hc):
         """get_gram -> gram_embedding (+BN) -> LayerScaleBlockClassAttn -> this head's classifier input"""
@@ -898,8 +661,6 @@ class GAHeads(GroupMlp):
         # --- class-attention block
         pre = f'ga.{k}.'
         N = HW
-        pk, pv = P[pre + 'attn.k.weight'], P[pre + 'attn.v.weight']
-        assert pv.data_ptr() == pk.data_ptr() + pk.numel() * 4, 'k/v weights must be adjacent in the flat buffer'
         h['ao'] = self.act(pre + 'ao', (B, E))
         h['P'] = self.act(pre + 'P', (B, nh, N + 1), torch.float32)
         if self.shared_tok:
@@ -932,7 +693,7 @@ class GAHeads(GroupMlp):
             # buffer, so together they already are the stacked [2E, cout] matrix
             Wkv = self.buf('w.' + pre + 'kv', (2 * E, cout))
             WkvT = self.buf('wT.' + pre + 'kv', (cout, 2 * E)) if T else None
-            self.prep.weight_prep(pk, 1, 2 * E, cout, 1, 1, dt, out=Wkv, ldo=cout, outT=WkvT, ldt=2 * E if T else 0,
+            self.prep.weight_prep(P[pre + 'attn.k.weight'], 1, 2 * E, cout, 1, 1, dt, out=Wkv, ldo=cout, outT=WkvT, ldt=2 * E if T else 0,
                                   label='prep.' + pre + 'kv')
             h['Wkv'], h['WkvT'] = Wkv, WkvT
             h['kv'] = self.act(pre + 'kv', (B * (N + 1), 2 * E))
@@ -995,8 +756,7 @@ class GAHeads(GroupMlp):
         Bk.gemm(dpz, W[pre + 'attn.proj.weight.T'], dao, B, E, cout, dt, ldb=pad8(cout), label=pre + 'proj.dg')
         dq = self.tmp('dq', (B, E))
         # k, v are adjacent parameters -> their gradients form one [2E, cout] matrix in the flat gradient buffer
-        gk, gv = self.grad(pre + 'attn.k.weight'), self.grad(pre + 'attn.v.weight')
-        assert gv.data_ptr() == gk.data_ptr() + gk.numel() * 4, 'k/v gradients must be adjacent in the flat buffer'
+        self._kv_adjacent(pre + 'attn.k', pre + 'attn.v', of=self.grad)
         if self.shared_tok:
             g1, b1 = P[pre + 'norm1.weight'], P[pre + 'norm1.bias']
             dg1, db1 = self.grad(pre + 'norm1.weight'), self.grad(pre + 'norm1.bias')
@@ -1021,7 +781,7 @@ class GAHeads(GroupMlp):
         else:
             dkv = self.tmp('dkv', (B * (N + 1), 2 * E))
             Bk.class_attn_bwd(dao, h['q'], h['kv'], h['P'], dq, dkv, B, N + 1, nh, hd, h['scale'], dt, label=pre + 'attnb')
-            Bk.wgrad(dkv, h['un'], gk, B * (N + 1), 2 * E, cout, dt, label=pre + 'kv.wg')
+            Bk.wgrad(dkv, h['un'], self.grad(pre + 'attn.k.weight'), B * (N + 1), 2 * E, cout, dt, label=pre + 'kv.wg')
             dun = self.tmp('dun', (B * (N + 1), cout))
             Bk.gemm(dkv, h['WkvT'], dun, B * (N + 1), cout, 2 * E, dt, label=pre + 'kv.dg')
             Bk.wgrad(dq, h['un'], self.grad(pre + 'attn.q.weight'), B, E, cout, dt, ldx=(N + 1) * cout, label=pre + 'q.wg')
@@ -1072,82 +832,33 @@ class GAHeads(GroupMlp):
                     label=f'gram.{k}.dx')
         dg0 = self.tmp('dg0', (M4, g))
         self._gram_layer_bwd(h, dg1, dg0)
-        self._head_contract_bwd(h, k, dg0, M4)
-
-    def _head_contract_bwd(self, h, k, dg0, M4):
-        # gram_contraction BN backward into this head's column slice; the conv's wgrad / dgrad run once for all heads
-        g = self.cfg['gram_dim']
-        pre = f'gram_contraction.{k}.'
-        gcn = self.gcon
-        self._bn_bwd(pre + '1.', h['bn_gc'], dg0, None, h['gc'], gcn['dout'][:, k * g:], M4, g, ldx=gcn['ld'], lddx=gcn['ld'])
+        self._conv_stack_bn_bwd(self.gcon, k, h['bn_gc'], dg0, h['gc'])
 
     # ------------------------------------------------------------------------------------------
     # backward of the heads
     # ------------------------------------------------------------------------------------------
     def _build_heads_backward(self, x4, M4):
         """backward of _build_heads: classifiers, the heads, the shared parts; returns dx4 [M4, cout]"""
-        Bk, dt, B, P, W, cfg = self.bwd, self.dt, self.B, self.P, self.W, self.cfg
-        cout = self.cout
+        Bk, cfg = self.bwd, self.cfg
         K, NC = cfg['branches'], cfg['num_classes']
-        self.dlogits = self.buf('dlogits', (K, B, NC))
+        self.dlogits = self.buf('dlogits', (K, self.B, NC))
         Bk.zero(self.arena, label='zero.arena')
-        dx4 = self.tmp('dx4', (M4, cout))
-        # classifiers of the five heads: one batched wgrad and one batched dgrad
-        fa = self.fc_all
-        Gfc, gbfc = self.gbuf((K, NC, cout)), self.gbuf((K, NC))
-        Bk.wgrad(self.dlogits, fa['x'], Gfc, B, NC, cout, dt, batch=K, strideY=B * NC, strideX=B * cout, strideW=NC * cout,
-                 dbias=gbfc, strideDbias=NC, label='fc.all.wg')
-        for k in range(K):
-            Bk.axpy_f32(self.grad(f'fc.{k}.weight'), Gfc[k], 1.0, NC * cout)
-            Bk.axpy_f32(self.grad(f'fc.{k}.bias'), gbfc[k], 1.0, NC)
-        fa['dx'] = self.tmp('dcls2_all', (K, B, cout))
-        Bk.gemm(self.dlogits, fa['WT'], fa['dx'], B, cout, NC, dt, batch=K, strideA=B * NC, strideB=cout * pad8(NC),
-                ldb=pad8(NC), strideC=B * cout, label='fc.all.dg')
-        if self.shared_tok:     # written slice-wise by the heads, consumed after the loop
-            tk = self.tok
-            tk['dkv'] = self.tmp('dkv_all', (M4, tk['ld']))
-            tk['G'], tk['gb'] = self.gbuf((tk['ld'], cout)), self.gbuf((tk['ld'],))
-        self.gcon['dout'] = self.tmp('dgc_all', (M4, self.gcon['ld']))
-        for k in range(K):
-            if self.head_lanes > 1:
-                Bk.lane, self.tmp_prefix = 1 + k % self.head_lanes, f'h{k}.'
+        dx4 = self.tmp('dx4', (M4, self.cout))
+        self._fc_stack_bwd(self.fc_all, self.dlogits, 'all')
+        if self.shared_tok:
+            self._tok_stack_bwd_open(self.tok)
+        self._conv_stack_bwd_open(self.gcon)
+        for k in self._each_head(Bk, K):
             self._head_bwd(self.heads[k], self.dlogits[k], dx4, first=(k == 0))
-        Bk.lane, self.tmp_prefix = 0, ''
         self._contract_all_bwd(x4, dx4, M4)
         if self.shared_tok:
-            tk = self.tok
-            E2 = tk['E2']
-            # token rows of all heads at once: effective k|v weight gradients, then each head's norm1 fold undone ...
-            with self._wlane():
-                Bk.wgrad(tk['dkv'], tk['xn'], tk['G'], M4, tk['ld'], cout, dt, dbias=tk['gb'], label='ga.kv_all.wg')
-            for k in range(K):
-                pre = f'ga.{k}.'
-                Bk.weight_unfold(tk['G'][k * E2:], cout, E2, cout, gb=tk['gb'][k * E2:], W=self._pw(pre + 'attn.k.weight'),
-                                 cs=P[pre + 'norm1.weight'], v=P[pre + 'norm1.bias'], dW=self._pg(pre + 'attn.k.weight'),
-                                 d_cs=self.grad(pre + 'norm1.weight'), d_v=self.grad(pre + 'norm1.bias'), label=pre + 'kv.unf')
-
-            # ... and dx4 += LayerNorm'(gradient wrt the shared normalised tokens, summed over the heads by the K = 5*2E GEMM)
-            dxt = self.tmp('dxn_tok', (M4, cout))
-            Bk.gemm(tk['dkv'], tk['WT'], dxt, M4, cout, tk['ld'], dt, label='ga.kv_all.dg')
-            Bk.layernorm_bwd(dxt, tk['xn'], None, tk['rstd'], None, dx4, dx4, None, None, M4, cout, True, dt, label='ga.tok.lnb')
+            self._tok_stack_bwd_close(self.tok, dx4)
         return dx4
 
     def _contract_all_bwd(self, x4, dx4, M4):
-        """weight / data gradients of the five gram_contraction convs; FIRST writer of dx4 on the shared-token path"""
-        Bk, dt, cfg, cout = self.bwd, self.dt, self.cfg, self.cout
-        K = cfg['branches']
-        # gram_contraction convs of all heads: one wgrad (rows k*g.. -> head k's weight / bias gradient), one dgrad
-        gcn, g_ = self.gcon, cfg['gram_dim']
-        Gc, gbc = self.gbuf((gcn['ld'], cout)), self.gbuf((gcn['ld'],))
-        with self._wlane():
-            Bk.wgrad(gcn['dout'], x4, Gc, M4, gcn['ld'], cout, dt, dbias=gbc, label='gram_contraction.all.wg')
-        for k in range(K):
-            pre = f'gram_contraction.{k}.'
-            Bk.axpy_f32(self.grad(pre + '0.weight'), Gc[k * g_:], 1.0, g_ * cout)
-            Bk.axpy_f32(self.grad(pre + '0.bias'), gbc[k * g_:], 1.0, g_)
-        # the first writer of dx4 on the shared-token path (the per-head token_split of the other path has written it)
-        Bk.gemm(gcn['dout'], gcn['WT'], dx4, M4, cout, gcn['ld'], dt, R=None if self.shared_tok else dx4, ldr=cout,
-                label='gram_contraction.all.dg')
+        """weight / data gradients of the five gram_contraction convs; FIRST writer of dx4 on the shared-token path (the per-head
+        token_split of the other path has written it)"""
+        self._conv_stack_bwd_close(self.gcon, x4, dx4, R=None if self.shared_tok else dx4, ldr=self.cout)
 
 
 class GAEngine(ConvNeXtTrunk, GAHeads, EngineBase):

@@ -10,8 +10,8 @@ Data layout in HBM (bf16 mode; fp32 mode is identical with 4-byte elements):
   * gradients: fp32, ONE flat buffer aliased by every param.grad; the wgrad kernels atomically accumulate either
     directly into it or into a zeroed scratch arena of effective-weight gradients that ga_weight_unfold maps back.
 
-A family is `class XEngine(<builders...>, EngineBase)`: the builders (engine.ConvNeXtTrunk / GroupMlp / GAHeads, engine_map.MAPHead,
-engine_blocks.TransformerBlocks, engine_pit.PiTTrunk) are stateless classes of recording methods -- no __init__, attributes created by their own
+A family is `class XEngine(<builders...>, EngineBase)`: the builders (engine.ConvNeXtTrunk / GAHeads, engine_map.MAPHead,
+engine_heads.GroupMlp / HeadStacks, engine_blocks.TransformerBlocks, engine_pit.PiTTrunk) are stateless classes of recording methods -- no __init__, attributes created by their own
 build methods only -- and the family fills in the hooks `_drop_path_rates`, `_build` and, where it needs more gradient scratch,
 `_arena_extra`.  The constructor runs `_build()` and then the tail every plan ends with (`_finish`).
 

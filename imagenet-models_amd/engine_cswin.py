@@ -205,7 +205,8 @@ class CSWinEngine(TransformerBlocks, GAHeads, EngineBase):
         K, g_, gg = cfg['branches'], cfg['gram_dim'], cfg['gram_groups']
         gpo, cpi = g_ // gg, cout // gg
         assert g_ % gg == 0 and gpo % 8 == 0 and cpi % 8 == 0, 'grouped gram_contraction needs 8-aligned group widths'
-        gc = self.gcon = dict(ld=K * g_, gpo=gpo, cpi=cpi, dense=False)
+        gc = self.gcon = self._conv_stack('gram_contraction', M4, cout, g_, self._contraction_heads())
+        gc.update(gpo=gpo, cpi=cpi, dense=False)
         if dt == ops.GA_BF16 and os.environ.get('GAEXT_GC_DENSE', '1') != '0':
             # the five grouped convs as ONE dense product over block-diagonal weights ([K g_] x cout, zeros off the diagonal blocks):
             # 8 x the MACs of the grouped form, but one ring-form launch with N = 960 instead of 40 products with N = 24 whose 48-byte
@@ -246,31 +247,27 @@ class CSWinEngine(TransformerBlocks, GAHeads, EngineBase):
         K, g_, gg = cfg['branches'], cfg['gram_dim'], cfg['gram_groups']
         gcn = self.gcon
         gpo, cpi = gcn['gpo'], gcn['cpi']
-        Gc, gbc = self.gbuf((K * g_, cpi)), self.gbuf((K * g_,))
+        R = None if self.shared_tok else dx4     # the first launch is the first writer of dx4 on the shared-token path
+
         if gcn['dense']:
-            Gd = self.gbuf((K * g_, cout))
-            with self._wlane():
-                Bk.wgrad(gcn['dout'], x4, Gd, M4, K * g_, cout, dt, dbias=gbc, label='gram_contraction.all.wg')
-                Bk.blockdiag_f32(Gd, Gc, K * g_, gpo, gg, cpi, cout, to_diag=False, label='gram_contraction.all.wg.diag')
-            for k in range(K):
-                pre = f'gram_contraction.{k}.'
-                Bk.axpy_f32(self.grad(pre + '0.weight'), Gc[k * g_:], 1.0, g_ * cpi)
-                Bk.axpy_f32(self.grad(pre + '0.bias'), gbc[k * g_:], 1.0, g_)
-            Bk.gemm(gcn['dout'], gcn['WdT'], dx4, M4, cout, K * g_, dt, ldb=pad8(K * g_), R=None if self.shared_tok else dx4, ldr=cout,
-                    label='gram_contraction.all.dg')
-            return
-        with self._wlane():
-            Bk.wgrad(gcn['dout'], x4, Gc, M4, gpo, cpi, dt, ldy=K * g_, ldx=cout, ldw=cpi, batch=K * gg, strideY=gpo, strideX=cpi,
-                     x_batch_mod=gg, strideW=gpo * cpi, dbias=gbc, strideDbias=gpo, label='gram_contraction.all.wg')
-        for k in range(K):
-            pre = f'gram_contraction.{k}.'
-            Bk.axpy_f32(self.grad(pre + '0.weight'), Gc[k * g_:], 1.0, g_ * cpi)
-            Bk.axpy_f32(self.grad(pre + '0.bias'), gbc[k * g_:], 1.0, g_)
-        for k in range(K):   # grouped data gradient, one batched GEMM per head; the first one is the first writer of dx4
-            first = k == 0 and self.shared_tok
-            Bk.gemm(gcn['dout'][:, k * g_:], gcn['WT'][k], dx4, M4, cpi, gpo, dt, lda=K * g_, ldb=pad8(gpo), ldc=cout, batch=gg,
-                    strideA=gpo, strideB=cpi * pad8(gpo), strideC=cpi, R=None if first else dx4, ldr=cout, strideR=cpi,
-                    label=f'gram_contraction.{k}.dg')
+            def wgrad(Gc, gbc, label):
+                Gd = self.gbuf((K * g_, cout))
+                Bk.wgrad(gcn['dout'], x4, Gd, M4, K * g_, cout, dt, dbias=gbc, label=label)
+                Bk.blockdiag_f32(Gd, Gc, K * g_, gpo, gg, cpi, cout, to_diag=False, label=label + '.diag')
+
+            def dgrad(label):
+                Bk.gemm(gcn['dout'], gcn['WdT'], dx4, M4, cout, K * g_, dt, ldb=pad8(K * g_), R=R, ldr=cout, label=label)
+        else:
+            def wgrad(Gc, gbc, label):
+                Bk.wgrad(gcn['dout'], x4, Gc, M4, gpo, cpi, dt, ldy=K * g_, ldx=cout, ldw=cpi, batch=K * gg, strideY=gpo, strideX=cpi,
+                         x_batch_mod=gg, strideW=gpo * cpi, dbias=gbc, strideDbias=gpo, label=label)
+
+            def dgrad(label):       # grouped data gradient, one batched GEMM per head
+                for k in range(K):
+                    Bk.gemm(gcn['dout'][:, k * g_:], gcn['WT'][k], dx4, M4, cpi, gpo, dt, lda=K * g_, ldb=pad8(gpo), ldc=cout, batch=gg,
+                            strideA=gpo, strideB=cpi * pad8(gpo), strideC=cpi, R=R if k == 0 else dx4, ldr=cout, strideR=cpi,
+                            label=f'gram_contraction.{k}.dg')
+        self._conv_stack_bwd_close(gcn, x4, dx4, cin=cpi, wgrad=wgrad, dgrad=dgrad)
 
     # gram_layer[k] = CSWinBlock(gram_dim, 6 heads) at 14 x 14 (ga_cswin.py:564-574)
     def _gram_layer_fwd(self, h, k, Hc):

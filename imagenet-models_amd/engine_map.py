@@ -20,8 +20,9 @@ import os
 import torch
 
 from . import ops  # noqa: F401
-from .engine import ConvNeXtTrunk, GroupMlp
+from .engine import ConvNeXtTrunk
 from .engine_base import EngineBase, pad8
+from .engine_heads import HeadStacks, Stacked
 from .ops import Plan
 
 
@@ -38,7 +39,7 @@ class FBConvNeXtTrunk(ConvNeXtTrunk):
         return {f'stages.{i}.{j}.': float(pts[i][j]) for i in range(4) for j in range(dep[i])}
 
 
-class MAPHead(GroupMlp):
+class MAPHead(HeadStacks):
     """builder: MultiScale, the CAP groups and the NormHeads on a trunk's feature maps; with dropout in the head, its own mask
     sampling in front of the forward and the (org, avg) form of the fused loss"""
     HP = 'head.'        # parameter-name prefix of the MAPHead (MobileNetV1 holds it as `fc.`)
@@ -107,7 +108,7 @@ class MAPHead(GroupMlp):
 
     # ------------------------------------------------------------------------------------------
     def _build_map_head(self, x, M4, Hc):
-        cfg, B, T, F, dt, P = self.cfg, self.B, self.training, self.fwd, self.dt, self.P
+        cfg, B, T, F = self.cfg, self.B, self.training, self.fwd
         self._init_group_mlp()
         L, G, Tn, E, nh = cfg['last_dim'], cfg['n_groups'], cfg['n_tokens'], cfg['ca_dim'], cfg['num_heads']
         bp, NC = cfg['bp_dim'], cfg['num_classes']
@@ -138,94 +139,62 @@ class MAPHead(GroupMlp):
             self.drop['views'] = [dict(attn=buf[k * per:k * per + n_attn].view(B, Tq, nh, N),
                                        proj=buf[k * per + n_attn:k * per + n_attn + n_proj].view(B * Tq, L),
                                        mlp=buf[k * per + n_attn + n_proj:(k + 1) * per].view(B * Tq, Hm)) for k in range(G)]
-        # ---- the image rows of norm1(cat(x_cls, x_img)) are the same for every group: ONE LayerNorm, ONE stacked k|v GEMM
-        tk = self.tok = dict(xn=self.act('ca.tok.xn', (M4, L)), rstd=self.act('ca.tok.rstd', (M4,), torch.float32))
-        F.layernorm_fwd(x, None, None, tk['xn'], None, tk['rstd'], M4, L, 1e-6, dt, label='ca.tok.ln')
-        E2 = 2 * E
-        tk['E2'], tk['ld'] = E2, G * E2
-        tk['W'] = self.buf('w.ca.kv_all', (G * E2, L))
-        tk['WT'] = self.buf('wT.ca.kv_all', (L, G * E2)) if T else None
-        tk['b'] = self.buf('w.ca.bkv_all', (G * E2,), torch.float32)
+        # ---- the image rows of norm1(cat(x_cls, x_img)) are the same for every group: the shared-token k|v stack.
         # dim_mismatch (gram_dim != last_dim, map.py:85-90,165-177): the image rows have their own projections k2 | v2 and norm1_2,
         # the class rows (width gram_dim) q | k1 | v1 and norm1_1, and the attention output REPLACES the class rows
         mm = self.mm = cfg['gram_dim'] != L
-        self.kv_img, self.n1_img = ('attn.k2', 'norm1_2') if mm else ('attn.k', 'norm1')
-        for k in range(G):
-            ap = f'{self.HP}mmcap.mmcap.{k}.attention.0.'
-            kn, vn = ap + self.kv_img, ap + self.kv_img.replace('.k', '.v')
-            pk, pv, bk, bv = P[kn + '.weight'], P[vn + '.weight'], P[kn + '.bias'], P[vn + '.bias']
-            assert pv.data_ptr() == pk.data_ptr() + pk.numel() * 4 and bv.data_ptr() == bk.data_ptr() + bk.numel() * 4, \
-                'k / v weights (and biases) must be adjacent in the flat buffer'
-            self.prep.weight_prep(pk, 1, E2, L, 1, 1, dt, out=tk['W'][k * E2:], ldo=L, outT=tk['WT'][:, k * E2:] if T else None,
-                                  ldt=G * E2 if T else 0, cs=P[ap + self.n1_img + '.weight'], t_cols=E2, label='prep.' + ap + 'kv')
-            self.prep.bias_fold(pk, bk, None, P[ap + self.n1_img + '.bias'], tk['b'][k * E2:], E2, L)
-        tk['kv'] = self.act('ca.kv_all', (M4, G * E2))
-        F.gemm(tk['xn'], tk['W'], tk['kv'], M4, G * E2, L, dt, bias=tk['b'], label='ca.kv_all')
-        # ---- ch_reduction (conv1x1, no bias) of all groups: ONE stacked GEMM; group k owns columns [k*bp, (k+1)*bp)
-        gc = self.gcon = dict(ld=G * bp)
-        gc['W'] = self.buf('w.ch_reduction.all', (G * bp, L))
-        gc['WT'] = self.buf('wT.ch_reduction.all', (L, G * bp)) if T else None
-        gc['s'], gc['q'] = self._bn_pool(G * bp), self._bn_pool(G * bp)
-        for k in range(G):
-            gp = f'{self.HP}mmcap.mmcap.{k}.gram_token_extraction.'
-            self.prep.weight_prep(P[gp + 'ch_reduction.0.weight'], 1, bp, L, 1, 1, dt, out=gc['W'][k * bp:], ldo=L,
-                                  outT=gc['WT'][:, k * bp:] if T else None, ldt=G * bp if T else 0, t_cols=bp, label='prep.' + gp + 'chr')
-        gc['out'] = self.act('ch_reduction.all.out', (M4, G * bp))
-        F.gemm(x, gc['W'], gc['out'], M4, G * bp, L, dt, colsum=gc['s'] if T else None, colsumsq=gc['q'] if T else None,
-               label='ch_reduction.all')
+        kn, nn_ = ('attn.k2', 'norm1_2') if mm else ('attn.k', 'norm1')
+        aps = [f'{self.HP}mmcap.mmcap.{k}.attention.0.' for k in range(G)]
+        for ap in aps:
+            self._kv_adjacent(ap + kn, ap + kn.replace('.k', '.v'), bias=True)
+        self.tok = self._tok_stack_fwd('ca', x, M4, L, 2 * E, 1e-6,
+                                       [Stacked(ap + kn + '.weight', ap + kn + '.bias', norm=ap + nn_ + '.', pre=ap) for ap in aps])
+        # ---- ch_reduction (conv1x1, no bias) of all groups: group k owns columns [k*bp, (k+1)*bp) of the conv stack
+        gps = [f'{self.HP}mmcap.mmcap.{k}.gram_token_extraction.' for k in range(G)]
+        self.gcon = self._conv_stack_fwd('ch_reduction', x, M4, L, bp, [
+            Stacked(gp + 'ch_reduction.0.weight', norm=gp + 'ch_reduction.1.', pre=gp + 'chr.', prep='prep.' + gp + 'chr', bufs=gp + 'chr.')
+            for gp in gps])
         # ---- classifiers: heads (on T*L) of all groups as one batched GEMM, self_dt_heads (on L) as another
-        fo = self.fc_org = dict(x=self.act('fc.org.x', (G, B, Tn * L)))
-        fo['W'] = self.buf('w.fc.org', (G, NC, Tn * L))
-        fo['WT'] = self.buf('wT.fc.org', (G, Tn * L, pad8(NC))) if T else None
-        fo['b'] = self.buf('w.fc.org.b', (G, NC), torch.float32)
-        for k in range(G):
-            if hfn == 'split':
-                # SplitNormHead (map.py:415-441): sum_t head_t(LayerNorm_t(token t)).  The T LayerNorms run as ONE affine-free
-                # LayerNorm over the (B * T) token rows; their affine parts fold into the T linears, which then are one
-                # [NC][T * L] operand (column block t = head_t.weight * gamma_t) with bias sum_t (head_t.weight beta_t + bias_t)
-                fo['bt'] = self.buf('w.fc.org.bt', (G, Tn, NC), torch.float32)
-                wt = [self.buf(f'w.fc.org.split.{k}.{t}', (NC, L)) for t in range(Tn)]      # (weight_prep pads an output row to ldo: it
-                for t in range(Tn):                                                          # cannot write a column slice directly)
-                    self.prep.weight_prep(P[f'{self.HP}heads.{k}.head.{t}.weight'], 1, NC, L, 1, 1, dt, out=wt[t], ldo=L,
-                                          outT=fo['WT'][k][t * L:] if T else None, ldt=pad8(NC) if T else 0,
-                                          cs=P[f'{self.HP}heads.{k}.norm.{t}.weight'], label=f'prep.heads.{k}.{t}')
-                    self.prep.bias_fold(P[f'{self.HP}heads.{k}.head.{t}.weight'], P[f'{self.HP}heads.{k}.head.{t}.bias'], None,
-                                        P[f'{self.HP}heads.{k}.norm.{t}.bias'], fo['bt'][k, t], NC, L)
-                self.prep.flush('prep.split.')
-                for t in range(Tn):
-                    self.prep.copy2d(wt[t], L, fo['W'][k][:, t * L:], Tn * L, NC, L, dt, label=f'prep.heads.{k}.{t}.place')
-                self.prep.zero(fo['b'][k], label=f'prep.heads.{k}.b0')
-                for t in range(Tn):          # (one batch per term: the jobs of a batch run concurrently and these share a destination)
-                    self.prep.axpy_f32(fo['b'][k], fo['bt'][k, t], 1.0, NC)
-                    self.prep.flush(f'prep.split.sum{t}.')
-                continue
-            wn = f'{self.HP}heads.{k}.weight' if hfn == 'linear' else f'{self.HP}heads.{k}.head.weight'
-            self.prep.weight_prep(P[wn], 1, NC, Tn * L, 1, 1, dt, out=fo['W'][k], ldo=Tn * L,
-                                  outT=fo['WT'][k] if T else None, ldt=pad8(NC) if T else 0, label=f'prep.heads.{k}')
-            self.prep.bias_fold(None, P[wn[:-6] + 'bias'], None, None, fo['b'][k], NC, Tn * L)
+        wn = f'{self.HP}heads.%d.weight' if hfn == 'linear' else f'{self.HP}heads.%d.head.weight'
+        fo = self.fc_org = self._fc_stack('org', G, Tn * L, None if hfn == 'split' else [
+            Stacked(wn % k, (wn % k)[:-6] + 'bias', prep=f'prep.heads.{k}') for k in range(G)])
+        if hfn == 'split':
+            self._split_heads_prep(fo)
         if T and sdt:
-            fa = self.fc_avg = dict(x=self.act('fc.avg.x', (G, B, L)))
-            fa['W'] = self.buf('w.fc.avg', (G, NC, L))
-            fa['WT'] = self.buf('wT.fc.avg', (G, L, pad8(NC)))
-            fa['b'] = self.buf('w.fc.avg.b', (G, NC), torch.float32)
-            for k in range(G):
-                self.prep.weight_prep(P[f'{self.HP}self_dt_heads.{k}.head.weight'], 1, NC, L, 1, 1, dt, out=fa['W'][k], ldo=L,
-                                      outT=fa['WT'][k], ldt=pad8(NC), label=f'prep.self_dt_heads.{k}')
-                self.prep.bias_fold(None, P[f'{self.HP}self_dt_heads.{k}.head.bias'], None, None, fa['b'][k], NC, L)
+            self.fc_avg = self._fc_stack('avg', G, L, [
+                Stacked(f'{self.HP}self_dt_heads.{k}.head.weight', f'{self.HP}self_dt_heads.{k}.head.bias', prep=f'prep.self_dt_heads.{k}')
+                for k in range(G)])
         # ---- the groups: independent chains of small launches -> side lanes, own transients
         self.head_lanes = int(os.environ.get('GAEXT_HEAD_STREAMS', '4'))
         self.groups = []
-        for k in range(G):
-            if self.head_lanes > 1:
-                F.lane, self.tmp_prefix = 1 + k % self.head_lanes, f'h{k}.'
+        for k in self._each_head(F, G):
             self.groups.append(self._group_fwd(k, M4, Hc))
-        F.lane, self.tmp_prefix = 0, ''
-        F.gemm(fo['x'], fo['W'], self.logits, B, NC, Tn * L, dt, batch=G, strideA=B * Tn * L, strideB=NC * Tn * L, strideC=B * NC,
-               bias=fo['b'], strideBias=NC, c_f32=True, label='fc.org')
+        self._fc_stack_fwd(fo, self.logits)
         if T and sdt:
-            fa = self.fc_avg
-            F.gemm(fa['x'], fa['W'], self.logits[G:], B, NC, L, dt, batch=G, strideA=B * L, strideB=NC * L, strideC=B * NC,
-                   bias=fa['b'], strideBias=NC, c_f32=True, label='fc.avg')
+            self._fc_stack_fwd(self.fc_avg, self.logits[G:])
+
+    def _split_heads_prep(self, fo):
+        """SplitNormHead (map.py:415-441) into the classifier stack `fo`: sum_t head_t(LayerNorm_t(token t)).  The T LayerNorms run
+        as ONE affine-free LayerNorm over the (B * T) token rows; their affine parts fold into the T linears, which then are one
+        [NC][T * L] operand (column block t = head_t.weight * gamma_t) with bias sum_t (head_t.weight beta_t + bias_t)"""
+        cfg, dt, P, T = self.cfg, self.dt, self.P, self.training
+        L, G, Tn, NC = cfg['last_dim'], cfg['n_groups'], cfg['n_tokens'], cfg['num_classes']
+        fo['bt'] = self.buf('w.fc.org.bt', (G, Tn, NC), torch.float32)
+        for k in range(G):
+            wt =[self.buf(f'w.fc.org.split.{k}.{t}', (NC, L)) for t in range(Tn)]      # (weight_prep pads an output row to ldo: it
+            for t in range(Tn):                                                          # cannot write a column slice directly)
+                self.prep.weight_prep(P[f'{self.HP}heads.{k}.head.{t}.weight'], 1, NC, L, 1, 1, dt, out=wt[t], ldo=L,
+                                      outT=fo['WT'][k][t * L:] if T else None, ldt=pad8(NC) if T else 0,
+                                      cs=P[f'{self.HP}heads.{k}.norm.{t}.weight'], label=f'prep.heads.{k}.{t}')
+                self.prep.bias_fold(P[f'{self.HP}heads.{k}.head.{t}.weight'], P[f'{self.HP}heads.{k}.head.{t}.bias'], None,
+                                    P[f'{self.HP}heads.{k}.norm.{t}.bias'], fo['bt'][k, t], NC, L)
+            self.prep.flush('prep.split.')
+            for t in range(Tn):
+                self.prep.copy2d(wt[t], L, fo['W'][k][:, t * L:], Tn * L, NC, L, dt, label=f'prep.heads.{k}.{t}.place')
+            self.prep.zero(fo['b'][k], label=f'prep.heads.{k}.b0')
+            for t in range(Tn):          # (one batch per term: the jobs of a batch run concurrently and these share a destination)
+                self.prep.axpy_f32(fo['b'][k], fo['bt'][k, t], 1.0, NC)
+                self.prep.flush(f'prep.split.sum{t}.')
 
     # ------------------------------------------------------------------------------------------
     def _group_fwd(self, k, M4, Hc):
@@ -242,13 +211,7 @@ class MAPHead(GroupMlp):
         gcn = self.gcon
         # --- ch_reduction BN on this group's column slice
         h['gc'] = gcn['out'][:, k * bp:]
-        bn = dict(s=gcn['s'][k * bp:(k + 1) * bp], q=gcn['q'][k * bp:(k + 1) * bp],
-                  mean=self.buf(gp + 'chr.bmean', (bp,), torch.float32), rstd=self.buf(gp + 'chr.brstd', (bp,), torch.float32),
-                  scale=self.buf(gp + 'chr.scale', (bp,), torch.float32), shift=self.buf(gp + 'chr.shift', (bp,), torch.float32))
-        h['bn_gc'] = bn
-        self._bn_finalize(gp + 'ch_reduction.1.', bn, M4, bp)
-        h['g0'] = self.buf(gp + 'g0', (M4, bp))
-        F.affine_act(h['gc'], bn['scale'], bn['shift'], None, h['g0'], M4, bp, False, dt, ldx=gcn['ld'], label=gp + 'chr.bn')
+        h['bn_gc'], h['g0'] = self._conv_stack_bn_fwd(gcn, k, h['gc'], gp + 'g0')
         # --- Gram (x / hw on both factors, map.py:217-218) -> packed, normalised, token-interleaved vector
         h['alpha'] = 1.0 / (HW * HW)
         Gm = self.tmp('gramG', (B, bp, bp), torch.float32)
@@ -288,8 +251,7 @@ class MAPHead(GroupMlp):
         h['kvc'] = self.act(ap + 'kvc', (R, E2))
         if mm:       # class rows: k1 | v1 (adjacent in the flat buffer) with norm1_1 folded
             pk, bk = P[ap + 'attn.k1.weight'], P[ap + 'attn.k1.bias']
-            assert P[ap + 'attn.v1.weight'].data_ptr() == pk.data_ptr() + pk.numel() * 4
-            assert P[ap + 'attn.v1.bias'].data_ptr() == bk.data_ptr() + bk.numel() * 4
+            self._kv_adjacent(ap + 'attn.k1', ap + 'attn.v1', bias=True)
             h['Wkvc'] = self.buf('w.' + ap + 'kv1', (E2, gd))
             h['WkvcT'] = self.buf('wT.' + ap + 'kv1', (gd, E2)) if T else None
             h['bkvc'] = self.buf('w.' + ap + 'bkv1', (E2,), torch.float32)
@@ -457,71 +419,39 @@ class MAPHead(GroupMlp):
         dg0 = self.tmp('dg0', (M4, bp))
         Bk.gemm(h['g0'], S, dg0, HW, bp, bp, dt, batch=B, strideA=HW * bp, strideB=bp * bp, strideC=HW * bp, alpha=h['alpha'],
                 label=f'gram.{k}.dx')
-        gcn = self.gcon
-        self._bn_bwd(gp + 'ch_reduction.1.', h['bn_gc'], dg0, None, h['gc'], gcn['dout'][:, k * bp:], M4, bp, ldx=gcn['ld'],
-                     lddx=gcn['ld'])
+        self._conv_stack_bn_bwd(self.gcon, k, h['bn_gc'], dg0, h['gc'])
+
+    def _split_heads_unfold(self, Gfc, gbfc, _):
+        """SplitNormHead: the LayerNorm fold undone per token: dW_t, d(bias_t), d(gamma_t), d(beta_t)"""
+        cfg, Bk, P = self.cfg, self.bwd, self.P
+        L, G, Tn, NC = cfg['last_dim'], cfg['n_groups'], cfg['n_tokens'], cfg['num_classes']
+        for k in range(G):
+            for t in range(Tn):
+                hk = f'{self.HP}heads.{k}.'
+                Bk.weight_unfold(Gfc[k][:, t * L:], Tn * L, NC, L, gb=gbfc[k], W=P[hk + f'{self.HP}{t}.weight'], b=P[hk + f'{self.HP}{t}.bias'],
+                                 cs=P[hk + f'norm.{t}.weight'], v=P[hk + f'norm.{t}.bias'], dW=self.grad(hk + f'{self.HP}{t}.weight'),
+                                 db=self.grad(hk + f'{self.HP}{t}.bias'), d_cs=self.grad(hk + f'norm.{t}.weight'),
+                                 d_v=self.grad(hk + f'norm.{t}.bias'), label=hk + f'{t}.unf')
 
     def _build_head_backward(self, x, M4):
         """classifiers, the groups, ch_reduction / k|v stacks, MultiScale conv: everything of head.* ; returns dcat [M4, ctot], the
         gradient of the multi-scale concat (the trunk-specific part takes it from there)"""
-        Bk, dt, B, P, W, cfg = self.bwd, self.dt, self.B, self.P, self.W, self.cfg
-        L, G, Tn, E, NC, bp = cfg['last_dim'], cfg['n_groups'], cfg['n_tokens'], cfg['ca_dim'], cfg['num_classes'], cfg['bp_dim']
-        sdt, hfn = self.sdt, self.head_fn
+        Bk, dt, B, W, cfg = self.bwd, self.dt, self.B, self.W, self.cfg
+        L, G, NC, sdt = cfg['last_dim'], cfg['n_groups'], cfg['num_classes'], self.sdt
         self.dlogits = self.buf('dlogits', ((2 if sdt else 1) * G, B, NC))
         Bk.zero(self.arena, label='zero.arena')
         # classifiers: one batched wgrad + dgrad for the heads, one for the self_dt_heads
-        fcs = [(self.fc_org, self.dlogits[:G], 'heads', Tn * L)] + ([(self.fc_avg, self.dlogits[G:], 'self_dt_heads', L)] if sdt else [])
-        for fc, dl, name, cin in fcs:
-            Gfc, gbfc = self.gbuf((G, NC, cin)), self.gbuf((G, NC))
-            Bk.wgrad(dl, fc['x'], Gfc, B, NC, cin, dt, batch=G, strideY=B * NC, strideX=B * cin, strideW=NC * cin, dbias=gbfc,
-                     strideDbias=NC, label=f'fc.{name}.wg')
-            for k in range(G):
-                if name == 'heads' and hfn == 'split':      # undo the LayerNorm fold per token: dW_t, d(bias_t), d(gamma_t), d(beta_t)
-                    for t in range(Tn):
-                        hk = f'{self.HP}heads.{k}.'
-                        Bk.weight_unfold(Gfc[k][:, t * L:], Tn * L, NC, L, gb=gbfc[k], W=P[hk + f'{self.HP}{t}.weight'], b=P[hk + f'{self.HP}{t}.bias'],
-                                         cs=P[hk + f'norm.{t}.weight'], v=P[hk + f'norm.{t}.bias'], dW=self.grad(hk + f'{self.HP}{t}.weight'),
-                                         db=self.grad(hk + f'{self.HP}{t}.bias'), d_cs=self.grad(hk + f'norm.{t}.weight'),
-                                         d_v=self.grad(hk + f'norm.{t}.bias'), label=hk + f'{t}.unf')
-                    continue
-                wn = f'{self.HP}{name}.{k}.weight' if (name == 'heads' and hfn == 'linear') else f'{self.HP}{name}.{k}.head.weight'
-                Bk.axpy_f32(self.grad(wn), Gfc[k], 1.0, NC * cin)
-                Bk.axpy_f32(self.grad(wn[:-6] + 'bias'), gbfc[k], 1.0, NC)
-            fc['dx'] = self.tmp(f'dfc.{name}', (G, B, cin))
-            Bk.gemm(dl, fc['WT'], fc['dx'], B, cin, NC, dt, batch=G, strideA=B * NC, strideB=cin * pad8(NC), ldb=pad8(NC),
-                    strideC=B * cin, label=f'fc.{name}.dg')
-        tk = self.tok
-        tk['dkv'] = self.tmp('dkv_all', (M4, tk['ld']))
-        tk['G'], tk['gb'] = self.gbuf((tk['ld'], L)), self.gbuf((tk['ld'],))
-        self.gcon['dout'] = self.tmp('dgc_all', (M4, self.gcon['ld']))
-        for k in range(G):
-            if self.head_lanes > 1:
-                Bk.lane, self.tmp_prefix = 1 + k % self.head_lanes, f'h{k}.'
+        self._fc_stack_bwd(self.fc_org, self.dlogits[:G], 'heads', scatter=self._split_heads_unfold if self.head_fn == 'split' else None)
+        if sdt:
+            self._fc_stack_bwd(self.fc_avg, self.dlogits[G:], 'self_dt_heads')
+        self._tok_stack_bwd_open(self.tok)
+        self._conv_stack_bwd_open(self.gcon)
+        for k in self._each_head(Bk, G):
             self._group_bwd(self.groups[k], M4)
-        Bk.lane, self.tmp_prefix = 0, ''
-        # ch_reduction convs of all groups: one wgrad, one dgrad (first writer of dx)
-        gcn = self.gcon
-        Gc = self.gbuf((gcn['ld'], L))
-        with self._wlane():
-            Bk.wgrad(gcn['dout'], x, Gc, M4, gcn['ld'], L, dt, label='ch_reduction.all.wg')
-        for k in range(G):
-            Bk.axpy_f32(self.grad(f'{self.HP}mmcap.mmcap.{k}.gram_token_extraction.ch_reduction.0.weight'), Gc[k * bp:], 1.0, bp * L)
+        # ch_reduction convs of all groups (first writer of dx), then the image rows' k|v stack: dx += LN'(...)
         dx = self.tmp('dx_ms', (M4, L))
-        Bk.gemm(gcn['dout'], gcn['WT'], dx, M4, L, gcn['ld'], dt, label='ch_reduction.all.dg')
-        # image rows of all groups: effective k|v weight gradients, each group's norm1 fold undone; dx += LN'(...)
-        E2 = tk['E2']
-        with self._wlane():
-            Bk.wgrad(tk['dkv'], tk['xn'], tk['G'], M4, tk['ld'], L, dt, dbias=tk['gb'], label='ca.kv_all.wg')
-        for k in range(G):
-            ap = f'{self.HP}mmcap.mmcap.{k}.attention.0.'
-            kn, nn_ = ap + self.kv_img, ap + self.n1_img
-            Bk.weight_unfold(tk['G'][k * E2:], L, E2, L, gb=tk['gb'][k * E2:], W=P[kn + '.weight'], b=P[kn + '.bias'],
-                             cs=P[nn_ + '.weight'], v=P[nn_ + '.bias'], dW=self.grad(kn + '.weight'),
-                             db=self.grad(kn + '.bias'), d_cs=self.grad(nn_ + '.weight'), d_v=self.grad(nn_ + '.bias'),
-                             label=ap + 'kv.unf')
-        dxt = self.tmp('dxn_tok', (M4, L))
-        Bk.gemm(tk['dkv'], tk['WT'], dxt, M4, L, tk['ld'], dt, label='ca.kv_all.dg')
-        Bk.layernorm_bwd(dxt, tk['xn'], None, tk['rstd'], None, dx, dx, None, None, M4, L, True, dt, label='ca.tok.lnb')
+        self._conv_stack_bwd_close(self.gcon, x, dx)
+        self._tok_stack_bwd_close(self.tok, dx)
         # MultiScale (or channel_convertor): activation, BN, conv1x1
         ms = self.ms
         mp = ms['pre']
