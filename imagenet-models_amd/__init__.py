@@ -9,7 +9,7 @@ from . import ops  # noqa: F401
 
 __version__ = '0.1.0'
 
-from .registry import create_model, is_model, list_models, register_model  # noqa: E402,F401
+from .registry import create_model, is_model, list_models, model_img_size, register_model  # noqa: E402,F401
 from . import ga_convnext  # noqa: E402,F401  (registers the ga_convnext_* entry points)
 from .ga_convnext import GA_ConvNeXt  # noqa: E402,F401
 from . import ga_cswin  # noqa: E402,F401  (registers the ga_CSWin_* entry points)
@@ -35,7 +35,7 @@ from .random_erasing import RandomErasing  # noqa: E402,F401
 from .rand_augment import RandAugment  # noqa: E402,F401
 from .resize_crop import RaggedBatch, pack_images, parse_hw, synthetic_ragged, RandomResizedCrop, ResizeCenterCrop  # noqa: E402,F401
 from .jpeg import JpegDecoder  # noqa: E402,F401
-from .dataset import ImageFolder, FolderLoader, split_dir, evaluate_folder  # noqa: E402,F401
+from .dataset import ImageFolder, FolderLoader, split_dir, evaluate_folder, repeat_aug_indices  # noqa: E402,F401
 from .input_stage import InputStage  # noqa: E402,F401
 from .trainer import TrainStep, distribute_bn, make_buckets  # noqa: E402,F401
 from .comm import NativeComm  # noqa: E402,F401

@@ -255,6 +255,23 @@ def _device_counters(step_fn):
     return out
 
 
+def loader_order(loader):
+    """what the order a loader position counts in depends on beside (seed, epoch): the folder loader's repeated-augmentation
+    settings (0 / 256 for every loader that has none)"""
+    return {'aug_repeats': int(getattr(loader, 'aug_repeats', 0)), 'selected_round': int(getattr(loader, 'selected_round', 256))}
+
+
+def check_loader_order(ts, loader):
+    """a saved position is a position in the order it was saved under: a run with other repeated-augmentation settings is refused.
+    A train_state without the two keys was written by a loader without them: 0 / 256"""
+    saved = (int(ts.get('aug_repeats', 0)), int(ts.get('selected_round', 256)))
+    mine = (int(getattr(loader, 'aug_repeats', 0)), int(getattr(loader, 'selected_round', 256)))
+    if saved[0] != mine[0] or (saved[0] and saved[1] != mine[1]):
+        raise ValueError(f'the checkpoint was written with aug_repeats {saved[0]}, selected_round {saved[1]}, this run has aug_repeats '
+                         f'{mine[0]}, selected_round {mine[1]}: the loader position counts batches of another order '
+                         '(--no-resume-opt takes the weights and the epoch only)')
+
+
 def capture_train_state(step_fn, loader=None, epoch=0, batch=0, rank=0, world=1, group=None, device_counters=True):
     """everything beside weights, optimizer moments and EMA that decides the next step (module docstring), as plain data.
     epoch / batch: the loader position -- `batch` batches of `epoch` are consumed.  Every rank calls it (the host generator states
@@ -262,7 +279,7 @@ def capture_train_state(step_fn, loader=None, epoch=0, batch=0, rank=0, world=1,
     device_counters=False leaves the samplers' device counters out: CheckpointSaver adds them from its snapshot without a
     host read on the training thread."""
     ts = {'opt_steps': int(step_fn.opt.steps), 'micro': int(step_fn.micro),
-          'loader': {'epoch': int(epoch), 'batch': int(batch)}}
+          'loader': {'epoch': int(epoch), 'batch': int(batch)}, **loader_order(loader)}
     if step_fn.random_erasing is not None:
         ts['re_offset'] = int(step_fn.random_erasing.offset)
     if device_counters:
@@ -324,6 +341,7 @@ def resume_checkpoint(ck, model, optimizer=None, model_ema=None, step_fn=None, l
         _logger.info('the checkpoint has no train_state: weights, optimizer and epoch are resumed; generators, sampler counters and '
                      'the loader position start afresh')
         return start_epoch, 0
+    check_loader_order(ts, loader)
     if step_fn is not None:
         missing = restore_train_state(ts, step_fn, loader, rank, world)
         if missing:

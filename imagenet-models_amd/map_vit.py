@@ -8,7 +8,7 @@ import torch.nn as nn
 
 from .flat_model import FlatModel, Holder
 from .map_convnext import _MAPHead, _init_weights
-from .registry import register_model, reject_gram_fp64
+from .registry import register_model, reject_gram_fp64, set_img_size
 
 __all__ = ['MAP_ViT']
 
@@ -99,6 +99,9 @@ def _create(variant, pretrained=False, **kwargs):
 @register_model
 def map_vit_base_patch16_384(pretrained=False, **kwargs):
     return _create('map_vit_base_patch16_384', pretrained, img_size=384, patch_size=16, embed_dim=768, depth=12, num_heads=12, **kwargs)
+
+
+set_img_size('map_vit_base_patch16_384', 384)
 
 
 @register_model

@@ -96,6 +96,21 @@ def model_entrypoint(name):
     return _entrypoints[name]
 
 
+_img_size = {}      # name -> input side, for the names not built for 224 (a factory's module says so beside the factory)
+
+
+def set_img_size(name, size):
+    _img_size[name] = int(size)
+
+
+def model_img_size(name):
+    """the input side a registered name is built for (its cfg['img_size'] once created), known without creating it: a command line
+    is checked against it before any weight is allocated"""
+    if not is_model(name):
+        raise RuntimeError(f'Unknown model ({name}); known: {list_models()}')
+    return _img_size.get(name, 224)
+
+
 def reject_gram_fp64(variant, kwargs):
     """gram_fp64 is GA_ConvNeXt.get_gram's float64 branch (ga_convnext.py:456-457).  ga_cswin.get_gram and MAP's GramToken have no
     such branch in the reference, so every other family refuses the kwarg instead of swallowing it."""

@@ -61,6 +61,12 @@ class RaggedBatch:
             raise IndexError('a RaggedBatch has a batch dimension only')
         return len(self)
 
+    def take(self, index):
+        """entry k of the result is entry index[k] of this one, over the SAME data: entries may repeat, and those that do share one
+        region of the buffer (a file decoded once under several table rows)"""
+        index = np.asarray(index, dtype=np.int64).reshape(-1)
+        return RaggedBatch(self.data, self.offsets[index], self.heights[index], self.widths[index])
+
 
 _PACK = staging.Ring()
 

@@ -11,6 +11,8 @@ oracle timed by bench.py).
   python train.py /data/imagenet --model map_resnet50 -b 256 -j 8 --aa rand-m9-mstd0.5-inc1 --collate-mixup --reprob 0.25
       an image folder (DIR/train/<class>/*.jpg, DIR/validation/...): baseline JPEGs are entropy-decoded on -j host threads and
       rebuilt, cropped, resized and augmented on the device
+  python train.py /data/imagenet ... --aug-repeats 3 -tb 1024 --cooldown-epochs 10    timm's repeated-augmentation order, each distinct
+      file of a batch decoded once; --print-config prints what the flags resolve to and exits before a model is created
   python train.py /data/imagenet ... --output out --recovery-interval 500      out/last.pth.tar, checkpoint-N, model_best, and a recovery
       file every 500 optimizer steps, written behind the step
   python train.py /data/imagenet ... --output out --resume out/last.pth.tar    continue exactly: weights, optimizer, EMA, every random
@@ -19,6 +21,7 @@ oracle timed by bench.py).
 """
 import argparse
 import contextlib
+import json
 import logging
 import os
 import random
@@ -96,7 +99,33 @@ parser.add_argument('--synthetic-source', type=str, default=None, metavar='HxW',
                     '(uint8 HWC, heights and widths within [0.5, 1.5] of H and W) and the step starts with the random-resized crop + '
                     'flip on the device (default: None, the loader yields cropped batches)')
 parser.add_argument('--drop-path', type=float, default=None)
+parser.add_argument('--drop', type=float, default=None, metavar='PCT', help='Dropout rate, forwarded to the model factory as drop_rate '
+                    '(MAP/train.py:446) when given; a factory that has no such argument ends the run (default: not forwarded)')
+# repeated augmentation (timm RepeatAugSampler; GA/train.py:197 defaults to 3, MAP/train.py to 0, six of the seven MAP recipes pass 3)
+parser.add_argument('--aug-repeats', type=int, default=0, metavar='N', help='Number of augmentation repetitions: every image of the '
+                    'epoch\'s permutation N times in a row, the epoch cut back to the dataset\'s length; each distinct file of a batch '
+                    'is decoded once (folder loader only; default: 0 -- the reference defaults to 3 in GA/train.py and 0 in MAP/train.py)')
+parser.add_argument('--selected-round', type=int, default=256, metavar='N', help='with --aug-repeats: the epoch is rounded down to a '
+                    'multiple of N samples before it is split over the ranks, 0: not rounded (default: 256, timm\'s)')
 parser.add_argument('--grad-accumulation', type=int, default=1)
+parser.add_argument('-tb', '--total-batch-size', type=int, default=None, metavar='N', help='total batch size per optimizer step: sets '
+                    '--grad-accumulation to N // (batch size * ranks) and overrides it (MAP/train.py:406; default: not set)')
+parser.add_argument('--cooldown-epochs', type=int, default=0, metavar='N', help='epochs to run at --min-lr after the cosine schedule '
+                    'ends: the run has --epochs + N epochs (default: 0 -- the reference\'s is 10, so its 300-epoch recipes run 310)')
+# the per-epoch evaluation of a folder run (validate.py has the same two)
+parser.add_argument('--crop-pct', type=float, default=None, metavar='N', help='centre-crop fraction of the evaluation transform: the '
+                    'short side is resized to floor(img / crop_pct) (default: 0.875; the recipes pass 0.95 or 0.875)')
+parser.add_argument('--interpolation', type=str, default='bicubic', help='resize interpolation of the evaluation transform, bilinear or '
+                    'bicubic (default: bicubic)')
+parser.add_argument('--input-size', type=int, nargs=3, default=None, metavar=('C', 'H', 'W'), help='accepted when it is the size the '
+                    'model is built for (3 224 224 for most); other sizes are not built')
+parser.add_argument('--test-input-size', type=int, nargs=3, default=None, metavar=('C', 'H', 'W'), help='as --input-size, for the '
+                    'evaluation')
+parser.add_argument('--pin-mem', action='store_true', help='accepted for CLI compatibility (the staging ring is always pinned)')
+parser.add_argument('--log-wandb', action='store_true', help='accepted with a warning: wandb logging is not built')
+parser.add_argument('--project-name', default=None, help='accepted for CLI compatibility (the wandb project of a recipe)')
+parser.add_argument('--print-config', action='store_true', help='print the resolved settings as one JSON line and exit, before the '
+                    'model is created or a device touched')
 parser.add_argument('--GA_lam', type=float, default=0)
 parser.add_argument('--dec-lam', type=float, default=None, help='MAP: weight of the group-decorrelation KL term '
                     '(MAP/train_with_script.py:39, multi_group_loss); alias of --GA_lam for the map_* models')
@@ -243,6 +272,38 @@ def validate(model, loader, args, world):
     return OrderedDict([('top1', top1_m.avg), ('top5', top5_m.avg)])
 
 
+def check_input_sizes(args, img):
+    """--input-size / --test-input-size name the size the model is built for, or end the run"""
+    for flag, size in (('--input-size', args.input_size), ('--test-input-size', args.test_input_size)):
+        if size is not None and tuple(size) != (3, img, img):
+            raise SystemExit(f"train.py: {flag} {' '.join(str(v) for v in size)}: {args.model} is built for 3 {img} {img}; other "
+                             'sizes are not built')
+
+
+def resolve_config(args, world, rank, train_loader=None):
+    """the settings the flags resolve to, checked on the host before the model is created (what --print-config prints).  Sets
+    args.grad_accumulation from -tb and args.crop_pct to its default."""
+    if args.aug_repeats < 0 or args.selected_round < 0 or args.cooldown_epochs < 0:
+        raise SystemExit(f'train.py: --aug-repeats {args.aug_repeats}, --selected-round {args.selected_round} and --cooldown-epochs '
+                         f'{args.cooldown_epochs} are whole numbers of at least 0')
+    if args.total_batch_size is not None:
+        args.grad_accumulation = args.total_batch_size // (args.batch_size * world)
+        if args.grad_accumulation < 1:
+            raise SystemExit(f'train.py: -tb {args.total_batch_size} is less than one batch of every rank ({args.batch_size} x {world} '
+                             'rank(s)): no whole number of batches per optimizer step')
+    if args.crop_pct is None:
+        args.crop_pct = 0.875                  # timm's evaluation default
+    cfg = OrderedDict([('model', args.model), ('batch_size', args.batch_size), ('world_size', world),
+                       ('grad_accumulation', args.grad_accumulation), ('epochs', args.epochs + args.cooldown_epochs),
+                       ('cooldown_epochs', args.cooldown_epochs), ('aug_repeats', args.aug_repeats),
+                       ('selected_round', args.selected_round), ('crop_pct', args.crop_pct), ('interpolation', args.interpolation),
+                       ('drop', args.drop)])
+    if train_loader is not None:
+        cfg.update(train_images=len(train_loader.dataset), batches_per_epoch=len(train_loader),
+                   distinct_files_per_epoch=train_loader.distinct_files(0))
+    return cfg
+
+
 def main():
     logging.basicConfig(level=logging.INFO, format='%(message)s')
     args = parser.parse_args()
@@ -274,6 +335,26 @@ def main():
         raise SystemExit(f"train.py: --eval-metric {args.eval_metric!r}: 'top1', 'top5' or 'loss'")
     if args.checkpoint_hist is not None and args.checkpoint_hist < 1:
         raise SystemExit(f'train.py: --checkpoint-hist {args.checkpoint_hist}: at least 1')
+    if not A.is_model(args.model):
+        raise SystemExit(f'train.py: --model {args.model!r} is not a registered model')
+    check_input_sizes(args, A.model_img_size(args.model))
+    # the training order is planned on the host (the decoder joins the loader once it exists): a folder too small for its batch or
+    # for --selected-round ends the run here
+    loader = None
+    if folder is not None:
+        try:
+            loader = A.FolderLoader(train_set, args.batch_size, None, train=True, seed=args.seed, rank=rank, world=world,
+                                    aug_repeats=args.aug_repeats, selected_round=args.selected_round)
+        except ValueError as e:
+            raise SystemExit(f'train.py: {e}')
+    config = resolve_config(args, world, rank, loader)
+    if args.print_config:
+        print(json.dumps(config))
+        return
+    if args.log_wandb and rank == 0:
+        _logger.warning('--log-wandb: wandb logging is not built; the run logs to the console (and --output) only')
+    if args.aug_repeats and folder is None and rank == 0:
+        _logger.info('--aug-repeats %d has no effect with --synthetic: there are no files to repeat', args.aug_repeats)
     # the files are read here, on the host: one that is missing or does not load ends the run before the device is touched
     resume_ck = None
     for flag, path in (('--resume', args.resume), ('--initial-checkpoint', args.initial_checkpoint)):
@@ -300,9 +381,20 @@ def main():
         torch.manual_seed(A.saved_initial_seed(resume_state, rank))
     np.random.seed(args.seed + rank)          # timm random_seed(): mixup draws lam / boxes from numpy's global generator
     random.seed(args.seed + rank)             # ... and RandomErasing draws its boxes from Python's
-    model = A.create_model(args.model, pretrained=False, num_classes=args.num_classes, drop_path_rate=args.drop_path,
-                           math_mode='fp32' if args.fp32 else 'bf16', gram_fp64=True if args.gram_fp64 else None)
+    try:
+        model = A.create_model(args.model, pretrained=False, num_classes=args.num_classes, drop_rate=args.drop,
+                               drop_path_rate=args.drop_path, math_mode='fp32' if args.fp32 else 'bf16',
+                               gram_fp64=True if args.gram_fp64 else None)
+    except (TypeError, AssertionError) as e:
+        if args.drop is None:
+            raise
+        raise SystemExit(f'train.py: --drop {args.drop}: {args.model} does not take drop_rate: {e}')
     img = getattr(model, 'cfg', {}).get('img_size', 224)
+    check_input_sizes(args, img)
+    try:
+        eval_crop = A.ResizeCenterCrop(img, args.crop_pct, args.interpolation) if folder is not None else None
+    except ValueError as e:
+        raise SystemExit(f'train.py: --crop-pct / --interpolation: {e}')
     # the flag-dependent transforms, each built once, on the host: a flag they refuse ends the run before the device is touched
     # RandAugment as timm's create_transform builds it: fill = the rounded dataset mean, the interpolation of the geometric ops
     try:
@@ -346,6 +438,7 @@ def main():
         _logger.info('Model %s created, param count: %d', args.model, sum(p.numel() for p in model.parameters()))
     opt = A.create_optimizer_v2(model, opt=args.opt, lr=args.lr, weight_decay=args.weight_decay, momentum=args.momentum,
                                 eps=args.opt_eps, betas=tuple(args.opt_betas) if args.opt_betas else None)
+    # --cooldown-epochs run past t_initial, where the schedule holds lr_min
     sched = A.CosineLRScheduler(opt, t_initial=args.epochs, lr_min=args.min_lr, warmup_t=args.warmup_epochs,
                                 warmup_lr_init=args.warmup_lr) if args.sched == 'cosine' else None
     lam = args.dec_lam if args.dec_lam is not None else args.GA_lam
@@ -376,30 +469,32 @@ def main():
                           mixup_fn=mixup_fn, bce_target_thresh=args.bce_target_thresh, comm=comm, random_erasing=random_erasing,
                           collate_mixup=collate_mixup, auto_augment=auto_augment, crop=crop)
     model_ema = A.ModelEma(model, args.model_ema_decay) if args.model_ema else None
-    decoder = eval_crop = None
+    decoder = None
     if folder is not None:
         # the folder: the files' bytes -> JpegDecoder (host entropy stage on -j threads, reconstruction on the device) -> the crop
         if len(train_set.classes) > model.num_classes:
             raise SystemExit(f'train.py: {len(train_set.classes)} class directories, the model has {model.num_classes} classes '
                              '(--num-classes)')
-        decoder = A.JpegDecoder(threads=args.workers)
-        try:
-            loader = A.FolderLoader(train_set, args.batch_size, decoder, train=True, seed=args.seed, rank=rank, world=world)
-        except ValueError as e:
-            raise SystemExit(f'train.py: {e}')
+        loader.decoder = decoder = A.JpegDecoder(threads=args.workers)
         eval_loader = A.FolderLoader(val_set, args.batch_size, decoder, train=False, rank=rank, world=world)
-        eval_crop = A.ResizeCenterCrop(img)              # timm's evaluation defaults: crop_pct 0.875, bicubic
         if rank == 0:
             _logger.info('Folder %s: %d training images in %d classes, %d validation images; %d decoder threads', folder,
                          len(train_set), len(train_set.classes), len(val_set), decoder.threads)
+            if args.aug_repeats:
+                _logger.info('    --aug-repeats %d (selected_round %d): %d batches per epoch from %d distinct files on this rank, each '
+                             'distinct file of a batch decoded once', args.aug_repeats, args.selected_round,
+                             config['batches_per_epoch'], config['distinct_files_per_epoch'])
     else:
         loader = SyntheticLoader(args.batch_size, args.steps_per_epoch, model.num_classes, args.seed + rank, 'cuda', img,
                                  uint8=step_fn.input_stage.takes == 'uint8', source=source)
         eval_loader = SyntheticLoader(args.batch_size, max(1, args.steps_per_epoch // 10), model.num_classes, 7 + rank, 'cuda', img)
     start_epoch = start_batch = 0
     if resume_ck is not None:
-        start_epoch, start_batch = A.resume_checkpoint(resume_ck, model, opt, model_ema, step_fn, loader, rank, world,
-                                                       resume_opt=not args.no_resume_opt)
+        try:
+            start_epoch, start_batch = A.resume_checkpoint(resume_ck, model, opt, model_ema, step_fn, loader, rank, world,
+                                                           resume_opt=not args.no_resume_opt)
+        except ValueError as e:
+            raise SystemExit(f'train.py: --resume {args.resume!r}: {e}')
         resume_ck = resume_state = None
     if args.start_epoch is not None:
         start_epoch, start_batch = args.start_epoch, 0
@@ -427,7 +522,7 @@ def evaluate(model, eval_loader, eval_crop, args, world, folder):
 
 def train_loop(args, model, opt, sched, step_fn, model_ema, loader, eval_loader, eval_crop, decoder, folder, mixup, saver, start_epoch,
                start_batch, world, rank):
-    for epoch in range(start_epoch, args.epochs):
+    for epoch in range(start_epoch, args.epochs + args.cooldown_epochs):
         if sched is not None:
             sched.step(epoch)
         if mixup is not None and args.mixup_off_epoch and epoch >= args.mixup_off_epoch:
