@@ -115,25 +115,33 @@ __global__ __launch_bounds__(256) void ga_loss_kernel(const float* __restrict__ 
     if (threadIdx.x == 0) atomicAdd(loss, total);
 }
 
-// sum over heads + top-k (k <= 8) with lowest-index tie-break; one wave per sample.
+// sum over heads + top-k (any topk <= NC: one pass over the row per index, so the metric's k = 5 is what it is sized for) with
+// lowest-index tie-break; one wave per sample.  The row is kept in LDS as order-preserving unsigned keys: a larger float has a
+// larger key, -0 and +0 share one, NaN has the largest (torch.topk ranks NaN above +inf: a diverged run must still give valid
+// indices) and 0, which no value maps to, marks an index already taken.
+__device__ __forceinline__ unsigned topk_key(float s) {
+    if (s != s) return 0xffffffffu;
+    const unsigned u = __float_as_uint(s == 0.f ? 0.f : s);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);       // -inf -> 0x007fffff: every key is nonzero
+}
 __global__ __launch_bounds__(64) void heads_topk_kernel(const float* __restrict__ logits, int K, int B, int NC, int topk,
                                                         float* __restrict__ out_sum, int64_t* __restrict__ out_idx) {
-    extern __shared__ float sv[];  // [NC]
+    extern __shared__ unsigned sv[];  // [NC]
     const long b = blockIdx.x;
     const int lane = threadIdx.x;
     for (int c = lane; c < NC; c += 64) {
         float s = 0.f;
         for (int k = 0; k < K; ++k) s += logits[((long)k * B + b) * NC + c];
         if (out_sum) out_sum[b * NC + c] = s;
-        sv[c] = s != s ? INFINITY : s;   // torch.topk ranks NaN largest (a diverged run must still give valid indices)
+        sv[c] = topk_key(s);
     }
     __syncthreads();
     for (int t = 0; t < topk; ++t) {
-        float best = -INFINITY;
+        unsigned best = 0u;
         int bi = 0x7fffffff;
         for (int c = lane; c < NC; c += 64) {
-            const float v = sv[c];
-            if (v != v) continue;        // already taken
+            const unsigned v = sv[c];
+            if (v == 0u) continue;       // already taken
             if (v > best || (v == best && c < bi)) {
                 best = v;
                 bi = c;
@@ -141,7 +149,7 @@ __global__ __launch_bounds__(64) void heads_topk_kernel(const float* __restrict_
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(best, o, 64);
+            const unsigned ov = __shfl_xor(best, o, 64);
             const int oi = __shfl_xor(bi, o, 64);
             if (ov > best || (ov == best && oi < bi)) {
                 best = ov;
@@ -150,7 +158,7 @@ __global__ __launch_bounds__(64) void heads_topk_kernel(const float* __restrict_
         }
         if (lane == 0) {
             out_idx[b * topk + t] = bi;
-            if (bi < NC) sv[bi] = __builtin_nanf("");
+            if (bi < NC) sv[bi] = 0u;
         }
         __syncthreads();
     }

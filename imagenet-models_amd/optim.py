@@ -161,7 +161,12 @@ class FusedAdamW(_FlatOptimizer):
 
 class FusedLamb(_FlatOptimizer):
     """timm.optim.Lamb (bias correction, grad averaging, max_grad_norm 1.0, trust ratio where weight decay applies) -- the
-    optimizer of the published GA recipes (GA/README.md:26).  timm is un-vendored: semantics restated, parity unpinned."""
+    optimizer of the published GA recipes (GA/README.md:26).  timm is un-vendored: the semantics are restated from the published
+    algorithm in tests/_loss_optim_ref.py (lamb_step, float64), which is anchored to torch.optim.Adam where LAMB reduces to it
+    (no decay, no clip) and to AdamW's direction plus wd * p on one tensor; tests/test_loss_optim_edges_gpu.py holds m, v, the
+    update direction, both per-tensor norms and p of every step to that restatement within a derived rounding bound (global-norm
+    pre-clip on and off, the decay / no-decay split, one to three chunks per tensor, beta3 with and without grad averaging,
+    |p| = 0, zero gradients, weight_decay = 0).  Parity with timm's own code is not pinned: timm is not available here."""
     kind, moment_names = 'lamb', ('m', 'v')
     CHUNK = 16384
 

@@ -470,7 +470,8 @@ int ga_class_attn_bwd2(const void* dout, const void* q, const void* kv_cls, cons
  *   logits fp32 [K][B][NC]; target int64 [B]; *loss must be zeroed by the caller; dlogits (dtype) = grad * grad_scale */
 int ga_loss_fwd_bwd(const float* logits, const int64_t* target, float* loss, void* dlogits, int K, int B, int NC,
                     float lam, int kind, float smoothing, float grad_scale, int dtype, ga_stream_t stream);
-/* validate(): output = sum_k out_k.float(); top-k indices, ties -> lowest index  (GA/train.py:848-860) */
+/* validate(): output = sum_k out_k.float(); top-k indices, ties -> lowest index  (GA/train.py:848-860).  Any 1 <= topk <= NC
+ * <= 36000; a NaN sum ranks above +inf, as in torch.topk; out_sum (fp32 [B][NC]) may be NULL */
 int ga_heads_topk(const float* logits, int K, int B, int NC, int topk, float* out_sum, int64_t* out_idx,
                   ga_stream_t stream);
 
