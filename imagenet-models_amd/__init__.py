@@ -30,6 +30,7 @@ from . import map_resnet  # noqa: E402,F401  (registers the repaired name map_re
 from .map_resnet import MAP_ResNet  # noqa: E402,F401
 from .loss import ga_loss, heads_topk, accuracy_from_topk, map_loss, heads_mean_topk  # noqa: E402,F401
 from .optim import create_optimizer_v2, FusedSGD, FusedAdamW, FusedLamb, CosineLRScheduler  # noqa: E402,F401
+from .optim import FusedAdam, FusedRMSprop, FusedLion, FusedLars, StepLRScheduler, optimizer_config  # noqa: E402,F401
 from .mixup import FastCollateMixup, Mixup  # noqa: E402,F401
 from .random_erasing import RandomErasing  # noqa: E402,F401
 from .rand_augment import RandAugment  # noqa: E402,F401

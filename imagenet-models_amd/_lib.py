@@ -179,6 +179,9 @@ _SIGS = {
     'ga_heads_topk': ([vp, i32, i32, i32, i32, vp, vp, vp], i32),
     'ga_sgd_step': ([vp, vp, vp, vp, i64, i32, f32, vp], i32),
     'ga_adamw_step': ([vp, vp, vp, vp, vp, i64, f32, vp], i32),
+    'ga_adam_step': ([vp, vp, vp, vp, vp, i64, f32, vp], i32),
+    'ga_rmsprop_step': ([vp, vp, vp, vp, vp, i64, i32, f32, vp], i32),
+    'ga_lion_step': ([vp, vp, vp, vp, i64, f32, vp], i32),
     'ga_weight_prep_batch': ([vp, i32, vp], i32),
     'ga_weight_unfold_batch': ([vp, i32, vp], i32),
     'ga_small_batch': ([vp, i32, vp], i32),
@@ -268,6 +271,8 @@ _SIGS = {
     'ga_sumsq_f32': ([vp, i64, vp, vp], i32),
     'ga_lamb_stage1': ([vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp], i32),
     'ga_lamb_stage2': ([vp, vp, vp, vp, i32, vp, vp], i32),
+    'ga_lars_stage1': ([vp, vp, vp, i32, vp, vp], i32),
+    'ga_lars_stage2': ([vp, vp, vp, vp, vp, i32, vp, i32, i32, vp], i32),
     'ga_clip_grad_f32': ([vp, i64, vp, f32, i32, vp], i32),
     'ga_rowscale': ([vp, vp, vp, i64, i64, i32, vp], i32),
     'ga_cast_from_f32': ([vp, vp, i64, i32, vp], i32),

@@ -194,6 +194,66 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     }
 }
 
+// torch.optim.Adam: AdamW's step with the decay coupled into the gradient (include/gaext.h states the order)
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                   float* __restrict__ m, float* __restrict__ v,
+                                                   const float* __restrict__ hp, long n, float wd_mult) {
+    const float lr = hp[0], wd = hp[1] * wd_mult, b1 = hp[2], b2 = hp[3], eps = hp[4], bc1 = hp[5], bc2 = hp[6];
+    const float step = lr / bc1, rbc2 = rsqrtf(bc2);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const float pi = p[i];
+        const float gi = g[i] + wd * pi;
+        const float mi = b1 * m[i] + (1.f - b1) * gi;
+        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        m[i] = mi;
+        v[i] = vi;
+        p[i] = pi - step * mi / (sqrtf(vi) * rbc2 + eps);
+    }
+}
+
+// hp = {lr, weight_decay, momentum, alpha, eps, 0, 0, 0}.  TF: timm RMSpropTF (eps inside the root, lr inside the momentum buffer,
+// sq moved by its difference to g'^2), otherwise torch.optim.RMSprop; MOM: buf is given
+template <bool TF, bool MOM>
+__global__ __launch_bounds__(256) void rmsprop_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                      float* __restrict__ sq, float* __restrict__ buf,
+                                                      const float* __restrict__ hp, long n, float wd_mult) {
+    const float lr = hp[0], wd = hp[1] * wd_mult, mu = hp[2], oma = 1.f - hp[3], alpha = hp[3], eps = hp[4];
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const float pi = p[i];
+        const float gi = g[i] + wd * pi;
+        float si = sq[i], avg;
+        if (TF) {
+            si = si + oma * (gi * gi - si);
+            avg = sqrtf(si + eps);
+        } else {
+            si = alpha * si + oma * gi * gi;
+            avg = sqrtf(si) + eps;
+        }
+        sq[i] = si;
+        if (MOM) {
+            const float bi = mu * buf[i] + (TF ? lr * gi / avg : gi / avg);
+            buf[i] = bi;
+            p[i] = pi - (TF ? bi : lr * bi);
+        } else {
+            p[i] = pi - lr * gi / avg;
+        }
+    }
+}
+
+// timm Lion: hp = {lr, weight_decay, beta1, beta2, ...}; the update is lr * sign(b1 m + (1 - b1) g) from the OLD m
+__global__ __launch_bounds__(256) void lion_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   const float* __restrict__ hp, long n, float wd_mult) {
+    const float lr = hp[0], wd = hp[1] * wd_mult, b1 = hp[2], b2 = hp[3];
+    const float keep = 1.f - lr * wd;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const float gi = g[i], mi = m[i];
+        const float c = b1 * mi + (1.f - b1) * gi;
+        const float s = c > 0.f ? 1.f : (c < 0.f ? -1.f : 0.f);
+        p[i] = p[i] * keep - lr * s;
+        m[i] = mi + (1.f - b2) * (gi - mi);
+    }
+}
+
 }  // namespace
 
 extern "C" int ga_loss_fwd_bwd(const float* logits, const int64_t* target, float* loss, void* dlogits, int K, int B,
@@ -264,6 +324,35 @@ extern "C" int ga_adamw_step(float* p, const float* g, float* m, float* v, const
     hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, m, v, hp,
                        (long)n, wd_mult);
     return ga_check_launch("ga_adamw_step");
+}
+
+extern "C" int ga_adam_step(float* p, const float* g, float* m, float* v, const float* hp, int64_t n, float wd_mult,
+                            ga_stream_t stream) {
+    GA_REQUIRE(p && g && m && v && hp && n > 0, "ga_adam_step: bad args");
+    const int blocks = (int)std::max<long>(1, std::min<long>(8192, (n + 255) / 256));
+    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, m, v, hp,
+                       (long)n, wd_mult);
+    return ga_check_launch("ga_adam_step");
+}
+
+extern "C" int ga_rmsprop_step(float* p, const float* g, float* sq, float* buf, const float* hp, int64_t n, int tf,
+                               float wd_mult, ga_stream_t stream) {
+    GA_REQUIRE(p && g && sq && hp && n > 0 && (tf == 0 || tf == 1), "ga_rmsprop_step: bad args (buf alone may be NULL; tf is 0 or 1)");
+    const int blocks = (int)std::max<long>(1, std::min<long>(8192, (n + 255) / 256));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    auto* k = tf ? (buf ? rmsprop_kernel<true, true> : rmsprop_kernel<true, false>)
+                 : (buf ? rmsprop_kernel<false, true> : rmsprop_kernel<false, false>);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, s, p, g, sq, buf, hp, (long)n, wd_mult);
+    return ga_check_launch("ga_rmsprop_step");
+}
+
+extern "C" int ga_lion_step(float* p, const float* g, float* m, const float* hp, int64_t n, float wd_mult,
+                            ga_stream_t stream) {
+    GA_REQUIRE(p && g && m && hp && n > 0, "ga_lion_step: bad args");
+    const int blocks = (int)std::max<long>(1, std::min<long>(8192, (n + 255) / 256));
+    hipLaunchKernelGGL(lion_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, m, hp, (long)n,
+                       wd_mult);
+    return ga_check_launch("ga_lion_step");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -514,6 +603,82 @@ extern "C" int ga_lamb_stage2(float* p, const float* u, const float* hp, const i
     hipLaunchKernelGGL(lamb_stage2_kernel, dim3(nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, u, hp,
                        chunks, norms);
     return ga_check_launch("ga_lamb_stage2");
+}
+
+// ------------------------------------------------------------------------------------------------
+// LARS on the flat buffers (timm.optim.Lars; the large-batch ResNet recipe) over the same chunk table: stage 1 accumulates
+// sum p^2 / sum g^2 per tensor (one atomic per workgroup and norm), stage 2 forms the per-tensor trust ratio and applies the
+// SGD-momentum step.  include/gaext.h states the order.
+//   hp (device): [lr, wd, momentum, trust_coeff, eps, first_step, 0, 0]
+// ------------------------------------------------------------------------------------------------
+namespace {
+__global__ __launch_bounds__(256) void lars_stage1_kernel(const float* __restrict__ p, const float* __restrict__ g,
+                                                          const int* __restrict__ chunks, float* __restrict__ norms) {
+    __shared__ float red[2][4];
+    const int* c = chunks + 4 * blockIdx.x;
+    const long off = c[0];
+    const int len = c[1], tid = c[2];
+    float sp = 0.f, sg = 0.f;
+    for (int i = threadIdx.x; i < len; i += 256) {
+        const float pi = p[off + i], gi = g[off + i];
+        sp = fmaf(pi, pi, sp);
+        sg = fmaf(gi, gi, sg);
+    }
+    sp = wave_sum(sp);
+    sg = wave_sum(sg);
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = sp;
+        red[1][threadIdx.x >> 6] = sg;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2)
+        atomicAdd(norms + 2 * tid + threadIdx.x, red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3]);
+}
+
+template <bool MOM>
+__global__ __launch_bounds__(256) void lars_stage2_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                          const float* __restrict__ hp, const int* __restrict__ chunks,
+                                                          const float* __restrict__ norms, int nesterov, int trust_clip) {
+    const int* c = chunks + 4 * blockIdx.x;
+    const long off = c[0];
+    const int len = c[1], tid = c[2];
+    const float lr = hp[0], wd = hp[1], mu = hp[2], first = hp[5];
+    const bool adapt = c[3] && wd != 0.f;
+    float trust = 1.f;
+    if (adapt) {
+        const float wn = sqrtf(norms[2 * tid]), gn = sqrtf(norms[2 * tid + 1]);
+        if (wn > 0.f && gn > 0.f) trust = hp[3] * wn / (gn + wn * wd + hp[4]);
+        if (trust_clip) trust = fminf(trust / lr, 1.f);
+    }
+    for (int i = threadIdx.x; i < len; i += 256) {
+        const long e = off + i;
+        const float pi = p[e];
+        float d = adapt ? (g[e] + wd * pi) * trust : g[e];
+        if (MOM) {
+            const float bi = first != 0.f ? d : mu * buf[e] + d;
+            buf[e] = bi;
+            d = nesterov ? d + mu * bi : bi;
+        }
+        p[e] = pi - lr * d;
+    }
+}
+}  // namespace
+
+extern "C" int ga_lars_stage1(const float* p, const float* g, const int* chunks, int nchunks, float* norms, ga_stream_t stream) {
+    GA_REQUIRE(p && g && chunks && norms && nchunks > 0, "ga_lars_stage1: bad args");
+    hipLaunchKernelGGL(lars_stage1_kernel, dim3(nchunks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, chunks, norms);
+    return ga_check_launch("ga_lars_stage1");
+}
+
+extern "C" int ga_lars_stage2(float* p, const float* g, float* buf, const float* hp, const int* chunks, int nchunks,
+                              const float* norms, int nesterov, int trust_clip, ga_stream_t stream) {
+    GA_REQUIRE(p && g && hp && chunks && norms && nchunks > 0, "ga_lars_stage2: bad args (buf alone may be NULL)");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (buf)
+        hipLaunchKernelGGL(lars_stage2_kernel<true>, dim3(nchunks), dim3(256), 0, s, p, g, buf, hp, chunks, norms, nesterov, trust_clip);
+    else
+        hipLaunchKernelGGL(lars_stage2_kernel<false>, dim3(nchunks), dim3(256), 0, s, p, g, buf, hp, chunks, norms, nesterov, trust_clip);
+    return ga_check_launch("ga_lars_stage2");
 }
 
 

@@ -866,6 +866,15 @@ class Plan:
     def adamw_step(self, p, g, m, v, hp, n, wd_mult, label=None):
         self.record('ga_adamw_step', p, g, m, v, hp, n, wd_mult, label=label)
 
+    def adam_step(self, p, g, m, v, hp, n, wd_mult, label=None):
+        self.record('ga_adam_step', p, g, m, v, hp, n, wd_mult, label=label)
+
+    def rmsprop_step(self, p, g, sq, buf, hp, n, tf, wd_mult, label=None):
+        self.record('ga_rmsprop_step', p, g, sq, buf, hp, n, bool(tf), wd_mult, label=label)
+
+    def lion_step(self, p, g, m, hp, n, wd_mult, label=None):
+        self.record('ga_lion_step', p, g, m, hp, n, wd_mult, label=label)
+
     def drop_path_sample(self, out, keep, sites, B, seed, counter, label=None):
         self.record('ga_drop_path_sample', out, keep, sites, B, _u64(seed), counter, label=label)
 
@@ -888,6 +897,12 @@ class Plan:
 
     def lamb_stage2(self, p, u, hp, chunks, nchunks, norms, label=None):
         self.record('ga_lamb_stage2', p, u, hp, chunks, nchunks, norms, label=label)
+
+    def lars_stage1(self, p, g, chunks, nchunks, norms, label=None):
+        self.record('ga_lars_stage1', p, g, chunks, nchunks, norms, label=label)
+
+    def lars_stage2(self, p, g, buf, hp, chunks, nchunks, norms, nesterov, trust_clip, label=None):
+        self.record('ga_lars_stage2', p, g, buf, hp, chunks, nchunks, norms, bool(nesterov), bool(trust_clip), label=label)
 
     def lerp_f32(self, y, x, w, n, label=None):
         self.record('ga_lerp_f32', y, x, float(w), n, label=label)

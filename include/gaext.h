@@ -483,6 +483,27 @@ int ga_sgd_step(float* p, const float* g, float* buf, const float* hp, int64_t n
 int ga_adamw_step(float* p, const float* g, float* m, float* v, const float* hp, int64_t n, float wd_mult,
                   ga_stream_t stream);
 
+/* More flat fused steps, in the same form (flat fp32 [n], hp a device fp32[8] row, wd_mult 0 for the no-decay segment; one
+ * grid-stride kernel of at most 8192 x 256 threads each, no allocation, no host synchronisation, no atomics).  This comment is the
+ * specification: every line is one fp32 operation order.  g' = g + wd * wd_mult * p (coupled L2 decay).
+ *   ga_adam_step (torch.optim.Adam), hp = {lr, wd, beta1, beta2, eps, bc1 = 1-beta1^t, bc2 = 1-beta2^t, 0}:
+ *       m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g' g';  p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+ *   ga_rmsprop_step, hp = {lr, wd, momentum, alpha, eps, 0, 0, 0}; the momentum form runs where buf is given, buf = NULL is the
+ *   form without (the host passes NULL exactly when momentum is 0):
+ *     tf = 0 (torch.optim.RMSprop, not centered):  sq = alpha sq + (1 - alpha) g' g';  avg = sqrt(sq) + eps;
+ *       buf: buf = mu buf + g' / avg, p -= lr buf;   no buf: p -= lr g' / avg
+ *     tf = 1 (timm RMSpropTF, not centered, coupled decay, lr_in_momentum):  sq += (1 - alpha) (g' g' - sq);
+ *       avg = sqrt(sq + eps) -- eps INSIDE the root;   buf: buf = mu buf + lr g' / avg, p -= buf;   no buf: p -= lr g' / avg
+ *       sq starts at ONE (the caller fills it; torch's starts at zero)
+ *   ga_lion_step (timm Lion), hp = {lr, wd, beta1, beta2, 0, 0, 0, 0}; decoupled decay, the only step here without g':
+ *       p *= (1 - lr wd wd_mult);  c = b1 m + (1 - b1) g;  p -= lr sign(c), sign(0) = 0;  m = m + (1 - b2) (g - m)
+ *       (c is formed from the m the step starts with) */
+int ga_adam_step(float* p, const float* g, float* m, float* v, const float* hp, int64_t n, float wd_mult,
+                 ga_stream_t stream);
+int ga_rmsprop_step(float* p, const float* g, float* sq, float* buf, const float* hp, int64_t n, int tf, float wd_mult,
+                    ga_stream_t stream);
+int ga_lion_step(float* p, const float* g, float* m, const float* hp, int64_t n, float wd_mult, ga_stream_t stream);
+
 /* Batched variants: `jobs_dev` is a DEVICE-resident array of n descriptors (same structs as above); one launch
  * processes them all (grid.y = job).  Used for the ~270 small per-parameter jobs of a training step. */
 typedef struct {
@@ -506,6 +527,22 @@ int ga_lamb_stage1(const float* p, const float* g, float* m, float* v, float* u,
                    const int* chunks, int nchunks, float* norms, ga_stream_t stream);
 int ga_lamb_stage2(float* p, const float* u, const float* hp, const int* chunks, int nchunks, const float* norms,
                    ga_stream_t stream);
+
+/* LARS (timm.optim.Lars; always_adapt is not built) over LAMB's chunk table (one workgroup per chunk, the caller zeroes norms).
+ *   stage1: norms[2t] += sum p^2, norms[2t+1] += sum g^2 per tensor t.  Each workgroup adds its two partial sums with ONE atomic
+ *           each, as ga_lamb_stage1 does: a tensor of several chunks has its partials added in the order the workgroups arrive, so
+ *           two runs on the same inputs may differ in the last bits of its norms (and, through the trust ratio, of buf and p); a
+ *           tensor of one chunk is bit-reproducible.
+ *   stage2: hp (device fp32[8]) = {lr, wd, momentum, trust_coeff, eps, first_step, 0, 0}; the momentum form runs where buf is given
+ *           (buf = NULL exactly when momentum is 0).  A chunk is ADAPTED where its decay flag is set and wd != 0 (timm adapts only
+ *           where the group's weight_decay != 0):
+ *             w = sqrt(norms[2t]), q = sqrt(norms[2t+1]);  trust = trust_coeff w / (q + w wd + eps) where w > 0 and q > 0, else 1;
+ *             trust_clip: trust = min(trust / lr, 1);  d = (g + wd p) trust
+ *           every other chunk: d = g.  Then SGD momentum with dampening 0:
+ *             buf = first_step ? d : mu buf + d;  d = nesterov ? d + mu buf : buf;  p -= lr d        (no buf: p -= lr d) */
+int ga_lars_stage1(const float* p, const float* g, const int* chunks, int nchunks, float* norms, ga_stream_t stream);
+int ga_lars_stage2(float* p, const float* g, float* buf, const float* hp, const int* chunks, int nchunks, const float* norms,
+                   int nesterov, int trust_clip, ga_stream_t stream);
 
 /* gradient clipping on the flat fp32 gradient buffer (timm dispatch_clip_grad via NativeScaler, GA/train.py:312-333):
  *   ga_sumsq_f32: *out += sum x^2 (caller zeroes *out; under DDP call after the all-reduce);

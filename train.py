@@ -58,7 +58,12 @@ parser.add_argument('--opt-betas', type=float, nargs='+', default=None)
 parser.add_argument('--momentum', type=float, default=0.9)
 parser.add_argument('--weight-decay', type=float, default=2e-5)
 parser.add_argument('--lr', type=float, default=0.05)
-parser.add_argument('--sched', default='cosine')
+parser.add_argument('--sched', default='cosine', help='LR scheduler: "cosine" or "step" (default: "cosine"; any other name runs at a '
+                    'constant --lr)')
+parser.add_argument('--decay-epochs', type=float, default=100, metavar='N', help='--sched step: epochs between two decays, may be '
+                    'fractional (default: 100)')
+parser.add_argument('--decay-rate', '--dr', type=float, default=0.1, metavar='RATE', help='--sched step: the factor of one decay '
+                    '(default: 0.1)')
 parser.add_argument('--warmup-lr', type=float, default=1e-4)
 parser.add_argument('--min-lr', type=float, default=1e-6)
 parser.add_argument('--warmup-epochs', type=int, default=3)
@@ -280,6 +285,26 @@ def check_input_sizes(args, img):
                              'sizes are not built')
 
 
+def schedule_config(args):
+    """the learning-rate schedule --sched resolves to: cosine, step, or none (a constant --lr) for every name that is not built"""
+    warm = dict(warmup_epochs=args.warmup_epochs, warmup_lr=args.warmup_lr)
+    if args.sched == 'cosine':
+        return dict(kind='cosine', t_initial=args.epochs, min_lr=args.min_lr, **warm)
+    if args.sched == 'step':
+        return dict(kind='step', decay_epochs=args.decay_epochs, decay_rate=args.decay_rate, **warm)
+    return dict(kind='none')
+
+
+def create_scheduler(args, opt):
+    cfg = schedule_config(args)
+    if cfg['kind'] == 'cosine':         # --cooldown-epochs run past t_initial, where the schedule holds lr_min
+        return A.CosineLRScheduler(opt, t_initial=args.epochs, lr_min=args.min_lr, warmup_t=args.warmup_epochs, warmup_lr_init=args.warmup_lr)
+    if cfg['kind'] == 'step':
+        return A.StepLRScheduler(opt, decay_t=args.decay_epochs, decay_rate=args.decay_rate, warmup_t=args.warmup_epochs,
+                                 warmup_lr_init=args.warmup_lr)
+    return None
+
+
 def resolve_config(args, world, rank, train_loader=None):
     """the settings the flags resolve to, checked on the host before the model is created (what --print-config prints).  Sets
     args.grad_accumulation from -tb and args.crop_pct to its default."""
@@ -293,11 +318,17 @@ def resolve_config(args, world, rank, train_loader=None):
                              'rank(s)): no whole number of batches per optimizer step')
     if args.crop_pct is None:
         args.crop_pct = 0.875                  # timm's evaluation default
+    try:
+        optimizer = A.optimizer_config(args.opt, momentum=args.momentum, eps=args.opt_eps, betas=args.opt_betas)
+    except ValueError as e:
+        raise SystemExit(f'train.py: --opt: {e}')
+    if args.sched == 'step' and not args.decay_epochs > 0:
+        raise SystemExit(f'train.py: --decay-epochs {args.decay_epochs}: more than 0')
     cfg = OrderedDict([('model', args.model), ('batch_size', args.batch_size), ('world_size', world),
                        ('grad_accumulation', args.grad_accumulation), ('epochs', args.epochs + args.cooldown_epochs),
                        ('cooldown_epochs', args.cooldown_epochs), ('aug_repeats', args.aug_repeats),
                        ('selected_round', args.selected_round), ('crop_pct', args.crop_pct), ('interpolation', args.interpolation),
-                       ('drop', args.drop)])
+                       ('drop', args.drop), ('opt', args.opt.lower()), ('optimizer', optimizer), ('schedule', schedule_config(args))])
     if train_loader is not None:
         cfg.update(train_images=len(train_loader.dataset), batches_per_epoch=len(train_loader),
                    distinct_files_per_epoch=train_loader.distinct_files(0))
@@ -438,9 +469,7 @@ def main():
         _logger.info('Model %s created, param count: %d', args.model, sum(p.numel() for p in model.parameters()))
     opt = A.create_optimizer_v2(model, opt=args.opt, lr=args.lr, weight_decay=args.weight_decay, momentum=args.momentum,
                                 eps=args.opt_eps, betas=tuple(args.opt_betas) if args.opt_betas else None)
-    # --cooldown-epochs run past t_initial, where the schedule holds lr_min
-    sched = A.CosineLRScheduler(opt, t_initial=args.epochs, lr_min=args.min_lr, warmup_t=args.warmup_epochs,
-                                warmup_lr_init=args.warmup_lr) if args.sched == 'cosine' else None
+    sched = create_scheduler(args, opt)
     lam = args.dec_lam if args.dec_lam is not None else args.GA_lam
     # mixup / cutmix (GA/train.py:544-557): smoothing then lives in the dense target and the loss is SoftTargetCrossEntropy /
     # BinaryCrossEntropy on it (:616-621)
