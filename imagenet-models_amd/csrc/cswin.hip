@@ -1209,6 +1209,7 @@ extern "C" int ga_layernorm_gelu_fwd(const void* x, const float* w, const float*
                                      int64_t rows, int C, float eps, int dtype, ga_stream_t stream) {
     GA_REQUIRE(x && w && b && y && mean && rstd && rows > 0, "ga_layernorm_gelu_fwd: null operand");
     GA_REQUIRE(C >= 8 && C <= 512 && (C & (C - 1)) == 0, "ga_layernorm_gelu_fwd: C=%d must be a power of two in [8, 512]", C);
+    GA_REQUIRE(aligned16(x) && aligned16(y), "ga_layernorm_gelu_fwd: x / y must be 16-byte aligned");     // load8 / store8
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (dtype == GA_BF16) ln_gelu_fwd_t<bf16_t>(x, w, b, y, mean, rstd, rows, C, eps, s);
     else ln_gelu_fwd_t<float>(x, w, b, y, mean, rstd, rows, C, eps, s);
@@ -1220,6 +1221,7 @@ extern "C" int ga_layernorm_gelu_bwd(const void* g, const void* x, const float* 
                                      ga_stream_t stream) {
     GA_REQUIRE(g && x && mean && rstd && w && b && dx && dw && db && rows > 0, "ga_layernorm_gelu_bwd: null operand");
     GA_REQUIRE(C >= 8 && C <= 512 && (C & (C - 1)) == 0, "ga_layernorm_gelu_bwd: C=%d must be a power of two in [8, 512]", C);
+    GA_REQUIRE(aligned16(g) && aligned16(x) && aligned16(dx), "ga_layernorm_gelu_bwd: g / x / dx must be 16-byte aligned");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (dtype == GA_BF16) ln_gelu_bwd_t<bf16_t>(g, x, mean, rstd, w, b, dx, dw, db, rows, C, s);
     else ln_gelu_bwd_t<float>(g, x, mean, rstd, w, b, dx, dw, db, rows, C, s);

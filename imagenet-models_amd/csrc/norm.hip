@@ -16,7 +16,9 @@ int pick_group(int C, int epc) {
         // of each row, i.e. HALF of every 128-byte line, and the streaming (non-temporal) loads do not keep the line
         // for the instruction that wants the other half: FETCH_SIZE showed 1.73x the algorithmic bytes.  16 lanes per
         // row (12 active) make every instruction cover whole rows: 0.053 vs 0.072 ms forward, 0.132 vs 0.145 backward
-        return GA_KNOB("LN_G12", 16);
+        // (any other value than a dispatched group size would run the 64-lane kernel on an rpb computed for another G)
+        const int g = GA_KNOB("LN_G12", 16);
+        return g == 4 || g == 8 || g == 16 || g == 32 || g == 64 ? g : 16;
     }
     for (int g = 4; g <= 64; g <<= 1)
         if (kMaxChunks * g >= nch) return g;
@@ -32,6 +34,19 @@ __device__ __forceinline__ void ld_chunk_nt(const float* p, float v[4]) { load4(
 __device__ __forceinline__ void ld_chunk_nt(const bf16_t* p, float v[8]) { load8_nt(p, v); }
 __device__ __forceinline__ void st_chunk(float* p, const float v[4]) { store4(p, v); }
 __device__ __forceinline__ void st_chunk(bf16_t* p, const float v[8]) { store8(p, v); }
+
+// every tensor is read and written in 16-byte pieces (load4 / store4 of fp32, load8 / store8 of bf16; load8 / store8 of fp32 are two of
+// them; load4 / store4 of bf16 are 8-byte pieces): a base pointer off that boundary -- a column slice of a wider matrix that starts at
+// an odd chunk -- is a misaligned vector access.  fp32 parameter / statistics vectors are read by element: 4 bytes.
+bool aligned_to(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+template <typename... P> bool all16(P... p) { return (aligned_to(p, 16) && ...); }
+template <typename... P> bool all4(P... p) { return (aligned_to(p, 4) && ...); }
+
+// dynamic LDS a launch gets without opting its kernel into more (hipFuncAttributeMaxDynamicSharedMemorySize): 64 KB of the 160 KB
+constexpr size_t kLdsPlain = 64 * 1024;
+
+// parameter-gradient reduce of ln_bwd_kernel: [2][rpb][C] floats
+size_t ln_bwd_lds(int C, int epc) { return (size_t)2 * (256 / pick_group(C, epc)) * C * sizeof(float); }
 
 int grid_blocks(long work_items, int per_block, int max_blocks = 2048) {
     return (int)std::max<long>(1, std::min<long>(max_blocks, (work_items + per_block - 1) / per_block));
@@ -522,7 +537,7 @@ static int ln_bwd_t(const void* g, const void* x, const float* mean, const float
     const int wgs_knob = GA_KNOB("LN_BWD_WGS", 0);
     const int wgs = wgs_knob > 0 ? std::max(64, wgs_knob) : (C <= 128 ? 1024 : 512);
     dim3 grid(grid_blocks(rows, rpb, dw ? wgs : 4096)), block(256);
-    const size_t lds = dw ? (size_t)2 * rpb * C * sizeof(float) : 0;
+    const size_t lds = dw ? ln_bwd_lds(C, elt<T>::EPC) : 0;
     const int nch3 = C / elt<T>::EPC <= G ? 1 : (C / elt<T>::EPC <= 3 * G ? 2 : (C / elt<T>::EPC <= 4 * G ? 0 : 8));
     LN_DISPATCH(G, (w != nullptr || dw != nullptr), nch3, ln_bwd_kernel, grid, block, lds, s, (const T*)g, (const T*)x, mean, rstd, w, (const T*)dres, (T*)dx,
                 dw, db, (long)rows, C, xnorm, (T*)dx2, scale2, (long)rows_per_scale);
@@ -534,6 +549,7 @@ extern "C" int ga_layernorm_fwd(const void* x, const float* w, const float* b, v
     const int epc = dtype == GA_BF16 ? 8 : 4;   // whole 16-byte chunks
     GA_REQUIRE(x && y && rows > 0 && C > 0 && C % epc == 0 && pick_group(C, epc) > 0, "ga_layernorm_fwd: C=%d unsupported", C);
     GA_REQUIRE((w == nullptr) == (b == nullptr), "ga_layernorm_fwd: w and b must both be given or both NULL");
+    GA_REQUIRE(all16(x, y) && all4(w, b, mean, rstd), "ga_layernorm_fwd: x / y must be 16-byte aligned, fp32 vectors 4-byte aligned");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     return dtype == GA_BF16 ? ln_fwd_t<bf16_t>(x, w, b, y, mean, rstd, rows, C, eps, s)
                             : ln_fwd_t<float>(x, w, b, y, mean, rstd, rows, C, eps, s);
@@ -543,8 +559,12 @@ extern "C" int ga_layernorm_bwd(const void* g, const void* x, const float* mean,
                                 const void* dres, void* dx, float* dw, float* db, int64_t rows, int C,
                                 int x_is_normalized, int dtype, ga_stream_t stream) {
     const int epc = dtype == GA_BF16 ? 8 : 4;
-    GA_REQUIRE(g && x && rstd && dx && rows > 0 && C % epc == 0 && pick_group(C, epc) > 0, "ga_layernorm_bwd: bad args");
+    GA_REQUIRE(g && x && rstd && dx && rows > 0 && C > 0 && C % epc == 0 && pick_group(C, epc) > 0, "ga_layernorm_bwd: bad args");
     GA_REQUIRE(x_is_normalized || mean, "ga_layernorm_bwd: mean required");
+    GA_REQUIRE((dw == nullptr) == (db == nullptr), "%s: dw and db must both be given or both NULL", "ga_layernorm_bwd");
+    GA_REQUIRE(!dw || ln_bwd_lds(C, epc) <= kLdsPlain, "%s: C=%d too wide for the LDS parameter-gradient reduce (%zu B > %zu B)", "ga_layernorm_bwd", C,
+               ln_bwd_lds(C, epc), kLdsPlain);
+    GA_REQUIRE(all16(g, x, dres, dx) && all4(mean, rstd, w, dw, db), "%s: g / x / dres / dx must be 16-byte aligned, fp32 vectors 4-byte aligned", "ga_layernorm_bwd");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     return dtype == GA_BF16 ? ln_bwd_t<bf16_t>(g, x, mean, rstd, w, dres, dx, dw, db, rows, C, x_is_normalized, s)
                             : ln_bwd_t<float>(g, x, mean, rstd, w, dres, dx, dw, db, rows, C, x_is_normalized, s);
@@ -555,9 +575,14 @@ extern "C" int ga_layernorm_bwd_dp(const void* g, const void* x, const float* me
                                    int x_is_normalized, void* dx2, const float* scale2, int64_t rows_per_scale, int dtype,
                                    ga_stream_t stream) {
     const int epc = dtype == GA_BF16 ? 8 : 4;
-    GA_REQUIRE(g && x && rstd && dx && dx2 && scale2 && rows_per_scale > 0 && rows > 0 && C % epc == 0 && pick_group(C, epc) > 0,
+    GA_REQUIRE(g && x && rstd && dx && dx2 && scale2 && rows_per_scale > 0 && rows > 0 && C > 0 && C % epc == 0 && pick_group(C, epc) > 0,
                "ga_layernorm_bwd_dp: bad args");
     GA_REQUIRE(x_is_normalized || mean, "ga_layernorm_bwd_dp: mean required");
+    GA_REQUIRE((dw == nullptr) == (db == nullptr), "%s: dw and db must both be given or both NULL", "ga_layernorm_bwd_dp");
+    GA_REQUIRE(!dw || ln_bwd_lds(C, epc) <= kLdsPlain, "%s: C=%d too wide for the LDS parameter-gradient reduce (%zu B > %zu B)", "ga_layernorm_bwd_dp", C,
+               ln_bwd_lds(C, epc), kLdsPlain);
+    GA_REQUIRE(all16(g, x, dres, dx) && all4(mean, rstd, w, dw, db), "%s: g / x / dres / dx must be 16-byte aligned, fp32 vectors 4-byte aligned", "ga_layernorm_bwd_dp");
+    GA_REQUIRE(all16(dx2) && all4(scale2), "ga_layernorm_bwd_dp: dx2 must be 16-byte aligned, scale2 4-byte aligned");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     return dtype == GA_BF16 ? ln_bwd_t<bf16_t>(g, x, mean, rstd, w, dres, dx, dw, db, rows, C, x_is_normalized, s, dx2, scale2, rows_per_scale)
                             : ln_bwd_t<float>(g, x, mean, rstd, w, dres, dx, dw, db, rows, C, x_is_normalized, s, dx2, scale2, rows_per_scale);
@@ -568,6 +593,7 @@ extern "C" int ga_bn_finalize(const float* sum, const float* sumsq, int64_t n, c
                               float* rstd_out, float* scale, float* shift, int C, int training, ga_stream_t stream) {
     GA_REQUIRE(scale && shift && C > 0 && (training ? (sum && sumsq && n > 0) : (running_mean && running_var)),
                "ga_bn_finalize: bad args");
+    GA_REQUIRE(all4(sum, sumsq, w, b, running_mean, running_var, mean_out, rstd_out, scale, shift), "ga_bn_finalize: fp32 vectors must be 4-byte aligned");
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 128)), dim3(128), 0, reinterpret_cast<hipStream_t>(stream), sum,
                        sumsq, (float)n, w, b, eps, momentum, running_mean, running_var, mean_out, rstd_out, scale, shift,
                        C, training);
@@ -582,6 +608,9 @@ extern "C" int ga_affine_act(const void* x, const float* scale, const float* shi
     GA_REQUIRE(x && y && rows > 0 && C % 8 == 0 && ((scale == nullptr) == (shift == nullptr)) &&
                    rows * C / 8 < (1L << 31), "ga_affine_act: bad args");
     GA_REQUIRE(C <= 8192, "ga_affine_act: C=%d too large for the LDS coefficient table", C);
+    // div_small: the quotient of row / rows_per_scale through a float reciprocal, exact for row < 2^24 and a divisor > 0
+    GA_REQUIRE(!rowscale || (rows_per_scale > 0 && rows < (1L << 24)), "%s: rowscale needs rows_per_scale > 0 and rows < 2^24", "ga_affine_act");
+    GA_REQUIRE(all16(x, res, y) && all4(scale, shift, rowscale), "ga_affine_act: x / res / y must be 16-byte aligned, fp32 vectors 4-byte aligned");
     const long n8 = rows * C / 8;
     dim3 grid(grid_blocks(n8, 256, 2048)), block(256);
     const size_t lds = (size_t)2 * C * sizeof(float);
@@ -600,7 +629,13 @@ extern "C" int ga_bn_bwd_reduce(const void* dy, const void* y_relu, const void* 
                                 int dtype, int64_t ldx, ga_stream_t stream) {
     if (ldx == 0) ldx = C;
     GA_REQUIRE(ldx >= C && ldx % 4 == 0, "ga_bn_bwd_reduce: ldx must be a multiple of 4 and >= C");
-    GA_REQUIRE(dy && x && mean && rstd && s1 && s2 && rows > 0 && C % 4 == 0, "ga_bn_bwd_reduce: bad args");
+    GA_REQUIRE(dy && x && mean && rstd && s1 && s2 && rows > 0 && C > 0 && C % 4 == 0, "ga_bn_bwd_reduce: bad args");
+    GA_REQUIRE(!rowscale || rows_per_scale > 0, "ga_bn_bwd_reduce: rowscale needs rows_per_scale > 0");
+    {   // load4: 16 bytes of fp32, 8 bytes of bf16
+        const unsigned al = dtype == GA_BF16 ? 8 : 16;
+        GA_REQUIRE(aligned_to(dy, al) && aligned_to(y_relu, al) && aligned_to(x, al) && all4(mean, rstd, rowscale, s1, s2),
+                   "ga_bn_bwd_reduce: dy / y_relu / x must be %u-byte aligned, fp32 vectors 4-byte aligned", al);
+    }
     const int slices = cdiv(C, 64);
     dim3 grid(std::max(1, std::min<int>((int)((rows + 15) / 16), std::max(1, 1024 / slices))), slices), block(256);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -623,6 +658,10 @@ extern "C" int ga_bn_bwd_apply(const void* dy, const void* y_relu, const void* x
     GA_REQUIRE(dy && x && mean && rstd && s1 && s2 && dx && rows > 0 && C % 8 == 0 && n > 0 && rows * C / 8 < (1L << 31),
                "ga_bn_bwd_apply: bad args");
     GA_REQUIRE(C <= 4096, "ga_bn_bwd_apply: C=%d too large for the LDS coefficient table", C);
+    // div_small: the quotient of row / rows_per_scale through a float reciprocal, exact for row < 2^24 and a divisor > 0
+    GA_REQUIRE(!rowscale || (rows_per_scale > 0 && rows < (1L << 24)), "%s: rowscale needs rows_per_scale > 0 and rows < 2^24", "ga_bn_bwd_apply");
+    GA_REQUIRE(all16(dy, y_relu, x, dx) && all4(mean, rstd, w, s1, s2, rowscale),
+               "ga_bn_bwd_apply: dy / y_relu / x / dx must be 16-byte aligned, fp32 vectors 4-byte aligned");
     const long n8 = rows * C / 8;
     dim3 grid(grid_blocks(n8, 256, 2048)), block(256);
     const size_t lds = (size_t)4 * C * sizeof(float);

@@ -355,6 +355,9 @@ int ga_subsample2_bwd(const void* dy, void* dx, int B, int H, int W, int C, int 
  *   fwd: y = (x-mean)*rstd [*w + b];  saves mean/rstd fp32 [rows] (each may be NULL).
  *   bwd: xhat = x_is_normalized ? x : (x-mean)*rstd;
  *        dx = rstd * (g*w - mean_c(g*w) - xhat*mean_c(g*w*xhat)) (+ dres);  dw[c] += sum g*xhat; db[c] += sum g
+ *   C > 0, a multiple of 8 (bf16) / 4 (fp32), at most 4096 / 2048; w and b both or neither; dw and db both or neither, and with
+ *   them C up to the 64 KB of LDS their reduce takes (bf16: C <= 2048); x / y / g / dres / dx / dx2 16-byte aligned.
+ *   GA_ERR_BAD_ARG otherwise, nothing is launched.
  * ------------------------------------------------------------------------------------------------------------ */
 int ga_layernorm_fwd(const void* x, const float* w, const float* b, void* y, float* mean, float* rstd, int64_t rows,
                      int C, float eps, int dtype, ga_stream_t stream);
@@ -376,6 +379,8 @@ int ga_layernorm_bwd_dp(const void* g, const void* x, const float* mean, const f
  *               rowscale = the DropPath factor of the Bottleneck main branch, ga_convnext.py:310-311)
  *   bwd_reduce: s1[c] += sum g, s2[c] += sum g*xhat, g = dy * (y_relu > 0 if given) * rowscale
  *   bwd_apply:  dx = w*rstd*(g - s1/n - xhat*s2/n)
+ *   With a rowscale: rows_per_scale > 0, and rows < 2^24 for affine_act / bwd_apply.  Tensors 16-byte aligned (bwd_reduce in
+ *   bf16: 8-byte), column slices included; fp32 vectors 4-byte aligned.  GA_ERR_BAD_ARG otherwise, nothing is launched.
  * ------------------------------------------------------------------------------------------------------------ */
 int ga_bn_finalize(const float* sum, const float* sumsq, int64_t n, const float* w, const float* b, float eps,
                    float momentum, float* running_mean, float* running_var, float* mean_out, float* rstd_out,
