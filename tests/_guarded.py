@@ -1,5 +1,5 @@
 """NaN-filled guarded device buffers for the kernel edge tests (tests/test_attn_edges_gpu.py,
-tests/test_class_attn_mt_edges_gpu.py): a kernel that leaves an in-range element unwritten, or writes a pad column or a
+tests/test_class_attn_mt_edges_gpu.py, tests/test_gemm_forms_edges_gpu.py): a kernel that leaves an in-range element unwritten, or writes a pad column or a
 guard row, is caught by comparing bit patterns before and after."""
 import torch
 

@@ -312,7 +312,8 @@ def test_gemm_lds_dma_form_bf16(shape, form, knobs):
     Since the ring form became the default, forcing another form does not switch its heuristic off and it is tried first, so of the
     36 launches of a parameter (9 shapes x 4 epilogues) the named form takes: dma256 2 (the plain epilogue of 40100x264x520 and
     12500x3072x768), dma128 0, t256 0 (both: ring 34, pp 1, staged-96 1), pp 13, r3 36; the rest run on the ring form
-    (tools/gemm_forms.py --coverage).  Reaching the named forms needs NT_R3=0 beside these knobs: a follow-up."""
+    (tools/gemm_forms.py --coverage).  tests/test_gemm_forms_edges_gpu.py reaches every named form (NT_R3=0 and the
+    other forms' knobs off beside these), asserts the form of every launch and holds it per element to a float64 reference."""
     ops = _imp()
     if form == 'dma256':
         knobs(NT_DMA=2)      # every eligible launch, not only the shapes the heuristic picks

@@ -4,10 +4,12 @@
     python tools/gemm_forms.py                  # print the corpus with the form each descriptor gets        (no GPU needed)
     python tools/gemm_forms.py --check          # compare against tests/golden/gemm_forms.json, exit 1 on a difference
     python tools/gemm_forms.py --write [--models FILE]   # record corpus and answers in that file (FILE: a new --dump-models)
-    python tools/gemm_forms.py --coverage       # the forced-form GPU tests: how many launches reach the form the test names
+    python tools/gemm_forms.py --coverage       # the forced-form GPU tests: how many launches reach the form the test names, and
+                                                # tests/test_gemm_forms_edges_gpu.py: launches that reach a form of the named family
     python tools/gemm_forms.py --dump-models    # GPU machine: rebuild the model part of the corpus (plans only, no kernel runs)
 
-The corpus is (a) the descriptors of the forced-form GPU tests under their knob settings, restated here call by call, and (b) every
+The corpus is (a) the descriptors of the forced-form GPU tests under their knob settings, restated here call by call (those of
+tests/test_gemm_forms_edges_gpu.py come from the case table it shares with this tool, tests/_gemm_ref.py), and (b) every
 distinct ga_gemm / ga_wgrad descriptor of the engines of tools/plan_fingerprint.py's NAMED models (bf16 training step at the bench
 batch, default knobs).  Pointers are reduced to null-or-not plus their low 4 bits.  The answers are this library's own; on a
 machine without a GPU the selection assumes 256 compute units, the MI355X's count.
@@ -86,6 +88,16 @@ class Recorder(ops.Plan):
 
 
 OP = object()
+EDGES = 'test_gemm_form_at_its_edges'
+
+
+def edge_table():
+    """tests/_gemm_ref.py: the case table of tests/test_gemm_forms_edges_gpu.py"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('_gemm_ref', os.path.join(ROOT, 'tests', '_gemm_ref.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
 
 
 def test_cases():
@@ -162,6 +174,14 @@ def test_cases():
                 P = rec('test_stem_wgrad_forms' if bias else 'test_stem_wgrad_without_bias', STEM4_WGRAD_DIRECT=flag)
                 P.wgrad(OP, OP, OP, B * (H // 4) * (W // 4), N, 48, bf, dbias=bias, x_kind=ops.A_STEM4_NCHW, x_dims=(H, W, 3))
                 done(['STEM4_WGRAD_DIRECT'])
+        # tests/test_gemm_forms_edges_gpu.py: one table feeds the test and this corpus (tests/_gemm_ref.py)
+        G = edge_table()
+        for c, fam in G.PAIRS:
+            P = rec(f'{EDGES}[{fam}-{c.label}]', **G.FAMILIES[fam])
+            for epi in c.epis_of(fam):
+                kw = {k: (OP if isinstance(v, str) else v) for k, v in G.gemm_kwargs(c, epi, ops).items()}
+                P.gemm(OP, OP, OP, c.M, c.N, c.K, ops.ga_dtype(c.dt), **kw)
+            done(G.FAMILIES[fam])
     finally:
         ops._ptr, ops._NUM_CU = real_ptr, real_cus
     return cases
@@ -199,13 +219,25 @@ def dump_models():
 
 
 def coverage(cases, forms):
-    """per parameter of test_gemm_lds_dma_form_bf16: launches whose form is the one the parameter names"""
+    """per parameter of test_gemm_lds_dma_form_bf16: launches whose form is the one the parameter names; per family of
+    test_gemm_form_at_its_edges: launches whose form belongs to that family"""
     rows = {}
     for c, f in zip(cases, forms):
         if c['src'].startswith('test_gemm_lds_dma_form_bf16['):
             want = c['src'][c['src'].index('[') + 1:-1]
             hit, n = rows.get(want, (0, 0))
             rows[want] = (hit + (f[0].split(':')[0].split('x')[0] == want), n + 1)
+    for want, (hit, n) in rows.items():
+        print(f'| `{want}` | {hit} of {n} |')
+    # ... and per family of tests/test_gemm_forms_edges_gpu.py: launches that reach a form of that family
+    rows = {}
+    for c, f in zip(cases, forms):
+        if c['src'].startswith(EDGES + '['):
+            want = c['src'][c['src'].index('[') + 1:].split('-')[0]
+            hit, n = rows.get(want, (0, 0))
+            fam = f[0].split(':')[0].split('x')[0]
+            rows[want] = (hit + ((fam[:6] if want == 'staged' else fam) == want), n + 1)
+    print()
     for want, (hit, n) in rows.items():
         print(f'| `{want}` | {hit} of {n} |')
 
