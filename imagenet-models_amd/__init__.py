@@ -34,6 +34,7 @@ from .optim import FusedAdam, FusedRMSprop, FusedLion, FusedLars, StepLRSchedule
 from .mixup import FastCollateMixup, Mixup  # noqa: E402,F401
 from .random_erasing import RandomErasing  # noqa: E402,F401
 from .rand_augment import RandAugment  # noqa: E402,F401
+from .aug_splits import AugSplits  # noqa: E402,F401
 from .resize_crop import RaggedBatch, pack_images, parse_hw, synthetic_ragged, RandomResizedCrop, ResizeCenterCrop  # noqa: E402,F401
 from .jpeg import JpegDecoder  # noqa: E402,F401
 from .dataset import ImageFolder, FolderLoader, split_dir, evaluate_folder, repeat_aug_indices  # noqa: E402,F401

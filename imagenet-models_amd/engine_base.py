@@ -434,27 +434,37 @@ class EngineBase:
         """(per-head logits, extra logits, d logits, d extra, heads) of the fused loss: every row of `logits` is a head"""
         return self.logits, None, self.dlogits, None, self.logits.shape[0]
 
-    def build_loss(self, lam, kind=0, smoothing=0.0, grad_scale=1.0, dense=False, bce_threshold=-1.0):
+    def build_loss(self, lam, kind=0, smoothing=0.0, grad_scale=1.0, dense=False, bce_threshold=-1.0, num_splits=0, jsd_alpha=12.0):
         """fused loss writing d(loss)/d(logits) * grad_scale straight into the backward plan's input buffer; dense: the target
-        is a (B, NC) fp32 tensor (mixup / cutmix) instead of class indices"""
+        is a (B, NC) fp32 tensor (mixup / cutmix) instead of class indices.  kind 2: timm's JsdCrossEntropy(num_splits, jsd_alpha,
+        smoothing) per head on a split-major batch of num_splits augmentation splits (ga_loss_jsd_fwd_bwd; the kernel reads the
+        first B / num_splits labels of the target buffer)"""
         org, avg, dorg, davg, K = self._loss_operands()
         _, B, NC = self.logits.shape
+        if kind == 2 and (dense or num_splits < 2 or B % num_splits):
+            raise ValueError(f'the JSD loss runs on class indices and on a batch of num_splits >= 2 augmentation splits: batch {B}, '
+                             f'num_splits {num_splits}, {"dense" if dense else "class-index"} target')
         self.loss_buf = self.buf('loss', (1,), torch.float32)
         self.target_buf = self.buf('target.dense', (B, NC), torch.float32) if dense else self.buf('target', (B,), torch.int64)
         lp = Plan(name='loss')
         lp.zero(self.loss_buf)
-        lp.loss_dense_fwd_bwd(org, avg, None if dense else self.target_buf, self.target_buf if dense else None, self.loss_buf, dorg, davg,
-                              K, B, NC, float(lam), int(kind), float(smoothing), float(bce_threshold), float(grad_scale), self.dt)
+        if kind == 2:
+            lp.loss_jsd_fwd_bwd(org, avg, self.target_buf, self.loss_buf, dorg, davg, K, B, NC, int(num_splits), float(lam),
+                                float(smoothing), float(jsd_alpha), float(grad_scale), self.dt)
+        else:
+            lp.loss_dense_fwd_bwd(org, avg, None if dense else self.target_buf, self.target_buf if dense else None, self.loss_buf, dorg,
+                                  davg, K, B, NC, float(lam), int(kind), float(smoothing), float(bce_threshold), float(grad_scale), self.dt)
         self.loss_plan = lp
-        self.loss_cfg = (lam, kind, smoothing, grad_scale, dense, bce_threshold)
+        self.loss_cfg = (lam, kind, smoothing, grad_scale, dense, bce_threshold, num_splits, jsd_alpha)
 
-    def forward_loss(self, x, target, lam, kind=0, smoothing=0.0, grad_scale=1.0, bce_threshold=-1.0):
+    def forward_loss(self, x, target, lam, kind=0, smoothing=0.0, grad_scale=1.0, bce_threshold=-1.0, num_splits=0, jsd_alpha=12.0):
         """forward + loss (+ dlogits) without autograd; follow with backward_to(mark) ... backward_to('end'), or bwd.run().
         Returns the loss buffer.
-        target: class indices (B,) or a dense (B, NC) floating-point target"""
+        target: class indices (B,) or a dense (B, NC) floating-point target; kind 2 (JSD over num_splits augmentation splits): the
+        class indices of all B rows, split-major, as AugSplits repeats them"""
         dense = target.dim() == 2
-        if self.loss_cfg != (lam, kind, smoothing, grad_scale, dense, bce_threshold):
-            self.build_loss(lam, kind, smoothing, grad_scale, dense, bce_threshold)
+        if self.loss_cfg != (lam, kind, smoothing, grad_scale, dense, bce_threshold, num_splits, jsd_alpha):
+            self.build_loss(lam, kind, smoothing, grad_scale, dense, bce_threshold, num_splits, jsd_alpha)
         self.forward(x)              # (resets backward_to's position)
         self.target_buf.copy_(target, non_blocking=True)
         self.loss_plan.run()

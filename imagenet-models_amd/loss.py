@@ -8,7 +8,21 @@ import torch
 from . import ops
 from .ops import GA_F32, Plan
 
-_KINDS = {'ce': 0, 'bce': 1}
+_KINDS = {'ce': 0, 'bce': 1, 'jsd': 2}
+
+
+def _jsd_args(kind, target, B, num_splits):
+    """kind 'jsd' (timm JsdCrossEntropy per head, GA/train.py:613-615) runs on a split-major batch of num_splits augmentation
+    splits and on class indices: -> the int64 labels of the B / num_splits base samples"""
+    if num_splits is None or int(num_splits) < 2:
+        raise ValueError(f"kind='jsd' needs num_splits >= 2 (the augmentation splits of the batch), got {num_splits!r}")
+    if target.dim() != 1 or target.dtype != torch.int64:
+        raise TypeError("kind='jsd' takes int64 class indices: the Jensen-Shannon loss has no dense-target (mixup / cutmix) form")
+    if B % int(num_splits):
+        raise ValueError(f'a batch of {B} rows does not divide into num_splits={num_splits} augmentation splits')
+    if target.shape[0] not in (B, B // int(num_splits)):
+        raise ValueError(f'target of {target.shape[0]} labels for a batch of {B} rows in {num_splits} splits')
+    return target[:B // int(num_splits)].contiguous()
 
 
 def _split_target(target, B, NC):
@@ -25,10 +39,15 @@ def _split_target(target, B, NC):
 
 class _GALossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, target, lam, kind, smoothing, thr):
+    def forward(ctx, logits, target, lam, kind, smoothing, thr, num_splits=None, jsd_alpha=12.0):
         K, B, NC = logits.shape
         loss = torch.zeros(1, device=logits.device)
         dl = torch.empty_like(logits)
+        if kind == _KINDS['jsd']:
+            Plan(eager=True).loss_jsd_fwd_bwd(logits, None, _jsd_args(kind, target, B, num_splits), loss, dl, None, K, B, NC,
+                                              int(num_splits), float(lam), float(smoothing), float(jsd_alpha), 1.0, GA_F32)
+            ctx.save_for_backward(dl)
+            return loss[0]
         idx, dense = _split_target(target, B, NC)
         Plan(eager=True).loss_dense_fwd_bwd(logits, None, idx, dense, loss, dl, None, K, B, NC, float(lam), kind, float(smoothing),
                                             float(thr), 1.0, GA_F32)
@@ -38,7 +57,7 @@ class _GALossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (dl,) = ctx.saved_tensors
-        return dl * g, None, None, None, None, None
+        return dl * g, None, None, None, None, None, None, None
 
 
 def stack_heads(outputs):
@@ -50,14 +69,17 @@ def stack_heads(outputs):
     return torch.stack(list(outputs))
 
 
-def ga_loss(outputs, target, lam=0.0, kind='ce', smoothing=0.0, bce_target_thresh=None):
+def ga_loss(outputs, target, lam=0.0, kind='ce', smoothing=0.0, bce_target_thresh=None, num_splits=None, jsd_alpha=12.0):
     """outputs: list of K (B,NC) fp32 logits; target: int64 (B,) class indices, or a dense (B,NC) target as mixup / cutmix
-    produce (then `smoothing` is already inside the target, GA/train.py:617).  Returns the scalar GA loss (differentiable)."""
+    produce (then `smoothing` is already inside the target, GA/train.py:617).  Returns the scalar GA loss (differentiable).
+    kind='jsd': timm's JsdCrossEntropy(num_splits, jsd_alpha, smoothing) per head in place of the cross entropy, on a split-major
+    batch (row i + j B / num_splits is augmentation split j of base sample i); target: the labels of the base samples, or of
+    all B rows (repeated per split, as the loader yields them)."""
     logits = stack_heads(outputs)
     if not logits.is_cuda:
         raise RuntimeError('ga_loss runs on the HIP kernels only (no CPU fallback)')
     thr = -1.0 if bce_target_thresh is None else float(bce_target_thresh)
-    return _GALossFn.apply(logits.float().contiguous(), target, lam, _KINDS[kind], smoothing, thr)
+    return _GALossFn.apply(logits.float().contiguous(), target, lam, _KINDS[kind], smoothing, thr, num_splits, jsd_alpha)
 
 
 def heads_topk(outputs, k=5):
@@ -81,11 +103,17 @@ def accuracy_from_topk(idx, target, topk=(1, 5)):
 
 class _MAPLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, target, lam, kind, smoothing, G, thr):
+    def forward(ctx, logits, target, lam, kind, smoothing, G, thr, num_splits=None, jsd_alpha=12.0):
         n, B, NC = logits.shape
         loss = torch.zeros(1, device=logits.device)
         dl = torch.empty_like(logits)
         has_avg = n == 2 * G
+        if kind == _KINDS['jsd']:
+            Plan(eager=True).loss_jsd_fwd_bwd(logits[:G], logits[G:] if has_avg else None, _jsd_args(kind, target, B, num_splits), loss,
+                                              dl[:G], dl[G:] if has_avg else None, G, B, NC, int(num_splits), float(lam),
+                                              float(smoothing), float(jsd_alpha), 1.0, GA_F32)
+            ctx.save_for_backward(dl)
+            return loss[0]
         idx, dense = _split_target(target, B, NC)
         Plan(eager=True).loss_dense_fwd_bwd(logits[:G], logits[G:] if has_avg else None, idx, dense, loss, dl[:G],
                                             dl[G:] if has_avg else None, G, B, NC, float(lam), kind, float(smoothing), float(thr), 1.0,
@@ -96,12 +124,13 @@ class _MAPLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (dl,) = ctx.saved_tensors
-        return dl * g, None, None, None, None, None, None
+        return dl * g, None, None, None, None, None, None, None, None
 
 
-def map_loss(outputs, target, dec_lam=0.0, kind='ce', smoothing=0.0, bce_target_thresh=None):
+def map_loss(outputs, target, dec_lam=0.0, kind='ce', smoothing=0.0, bce_target_thresh=None, num_splits=None, jsd_alpha=12.0):
     """MAP/train.py:792-839 (`multi_group_loss`, distill_tokens == 0) on the fused HIP kernel.  outputs: the model's train-mode
-    list of [org_out, avg_out] pairs (or a plain list of logits: then it is the GA loss with lam = dec_lam)."""
+    list of [org_out, avg_out] pairs (or a plain list of logits: then it is the GA loss with lam = dec_lam).
+    kind='jsd', num_splits, jsd_alpha: as in ga_loss (JsdCrossEntropy as the `loss_fn` of MAP/train.py:817,821)."""
     if isinstance(outputs[0], (list, tuple)):
         G = len(outputs)
         base = getattr(outputs[0][0], '_ga_stack', None)
@@ -116,7 +145,7 @@ def map_loss(outputs, target, dec_lam=0.0, kind='ce', smoothing=0.0, bce_target_
     if not logits.is_cuda:
         raise RuntimeError('map_loss runs on the HIP kernels only (no CPU fallback)')
     thr = -1.0 if bce_target_thresh is None else float(bce_target_thresh)
-    return _MAPLossFn.apply(logits.float().contiguous(), target, dec_lam, _KINDS[kind], smoothing, G, thr)
+    return _MAPLossFn.apply(logits.float().contiguous(), target, dec_lam, _KINDS[kind], smoothing, G, thr, num_splits, jsd_alpha)
 
 
 def heads_mean_topk(outputs, k=5):

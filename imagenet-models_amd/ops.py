@@ -771,6 +771,12 @@ class Plan:
         self.record('ga_loss_dense_fwd_bwd', org, avg, target, dense, loss, dorg, davg, K, B, NC, lam, kind, smoothing, bce_threshold,
                     grad_scale, dtype, label=label)
 
+    def loss_jsd_fwd_bwd(self, org, avg, target, loss, dorg, davg, K, B, NC, num_splits, lam, smoothing, alpha, grad_scale, dtype,
+                         label=None):
+        """GA (avg None) / MAP loss with timm's JsdCrossEntropy per head on a split-major batch of num_splits augmentation splits"""
+        self.record('ga_loss_jsd_fwd_bwd', org, avg, target, loss, dorg, davg, K, B, NC, num_splits, lam, smoothing, alpha, grad_scale,
+                    dtype, label=label)
+
     def u8_normalize(self, x, out, mean, std, label=None):
         """uint8 (B, C, H, W) -> fp32, (x - mean[c]) / std[c]; mean / std: python sequences in 0..255 units"""
         B, CH, H, W = x.shape

@@ -13,7 +13,7 @@ import torch.distributed as dist
 
 from .input_stage import InputStage
 
-_KINDS = {'ce': 0, 'bce': 1}
+_KINDS = {'ce': 0, 'bce': 1, 'jsd': 2}
 
 BUCKET_ELEMS = 8 << 20     # 32 MB of fp32 per all-reduce: enough to run at link rate over xGMI, small enough to pipeline
 
@@ -68,9 +68,12 @@ class TrainStep:
     def __init__(self, model, optimizer, batch, lam=0.0, loss='ce', smoothing=0.0, grad_accumulation=1,
                  process_group=None, clip_grad=None, clip_mode='norm', broadcast_buffers=True, bucket_elems=BUCKET_ELEMS,
                  mixup_fn=None, bce_target_thresh=None, comm=None, force_buckets=False, nan_guard=False,
-                 overlap_optimizer=False, random_erasing=None, collate_mixup=None, auto_augment=None, crop=None):
+                 overlap_optimizer=False, random_erasing=None, collate_mixup=None, auto_augment=None, crop=None, aug_splits=None,
+                 jsd_alpha=12.0):
         """mixup_fn, random_erasing, collate_mixup, auto_augment, crop: the pieces of the input stage, which input_stage.InputStage
         runs in its one order ahead of the forward pass (their meaning and the order are described there).
+        aug_splits: an imagenet_models_amd.AugSplits(S) -- `batch` stays the number of rows the engine runs, a multiple of S; the
+        loader yields batch // S samples.  loss='jsd' (timm JsdCrossEntropy(S, jsd_alpha, smoothing) per head) needs it.
         comm: an imagenet_models_amd.NativeComm -- the gradient buckets (and the BatchNorm-buffer broadcast) go through the
         library's own RCCL entry points (ga_allreduce_bucket on a side stream) instead of torch.distributed.
         force_buckets: take the segmented-backward + bucketed-reduction path even with one rank (tests: the real collective
@@ -78,7 +81,16 @@ class TrainStep:
         nan_guard: the device-side counterpart of MAP/train.py:887-891 (all_gather of the loss + isnan + exit): the loss value
         rides in the LAST gradient bucket's reduction as one extra element; `last_loss_sum` (a device tensor, the sum of the
         ranks' scaled losses) can be inspected by the caller at its logging interval -- no host synchronisation per step."""
-        self.input_stage = InputStage(crop, auto_augment, collate_mixup, random_erasing, mixup_fn)
+        if loss not in _KINDS:
+            raise ValueError(f"TrainStep: loss {loss!r}: 'ce', 'bce' or 'jsd'")
+        if loss == 'jsd' and aug_splits is None:
+            raise ValueError("TrainStep: loss='jsd' is the consistency loss over augmentation splits: pass aug_splits=AugSplits(S)")
+        self.input_stage = InputStage(crop, auto_augment, collate_mixup, random_erasing, mixup_fn, aug_splits)
+        if aug_splits is not None and batch % aug_splits.num_splits:
+            raise ValueError(f'TrainStep: batch {batch} (the rows the engine runs) is not a multiple of the {aug_splits.num_splits} '
+                             'augmentation splits')
+        self.aug_splits, self.jsd_alpha = aug_splits, float(jsd_alpha)
+        self.num_splits = aug_splits.num_splits if aug_splits is not None else 0
         self.model, self.opt = model, optimizer
         self.eng = model.engine(batch, True)
         self.lam, self.kind, self.smoothing = lam, _KINDS[loss], smoothing
@@ -194,7 +206,10 @@ class TrainStep:
         # the reference divides the loss by grad_accumulation (train.py:750); DDP averages over ranks
         scale = 1.0 / (self.accum * self.world)
         x, target = self.input_stage(x, target, eng)
-        loss = eng.forward_loss(x, target, self.lam, self.kind, self.smoothing, scale, self.bce_threshold)
+        if self.kind == 2:
+            loss = eng.forward_loss(x, target, self.lam, 2, self.smoothing, scale, -1.0, self.num_splits, self.jsd_alpha)
+        else:
+            loss = eng.forward_loss(x, target, self.lam, self.kind, self.smoothing, scale, self.bce_threshold)
         if self.overlap_opt and last_micro:
             self._backward_with_updates()
             self.micro += 1

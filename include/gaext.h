@@ -657,6 +657,26 @@ int ga_map_loss_fwd_bwd(const float* org, const float* avg, const int64_t* targe
 int ga_loss_dense_fwd_bwd(const float* org, const float* avg, const int64_t* target, const float* dense, float* loss, void* dorg,
                           void* davg, int K, int B, int NC, float lam, int kind, float smoothing, float bce_threshold,
                           float grad_scale, int dtype, ga_stream_t stream);
+/* timm JsdCrossEntropy (--aug-splits S --jsd-loss, GA/train.py:559-561,613-615) in place of the per-head loss, fused with the same
+ * head-decorrelation and self-distillation terms as ga_map_loss_fwd_bwd.  The batch is split-major: row i + s Bs is split s of base
+ * sample i, Bs = B / num_splits; only target[0 .. Bs) is read.  With p_s = softmax of the rows of split s, per head:
+ *     CE_smooth(x_0, y) (mean over Bs; on = 1 - smoothing + smoothing / NC, off = smoothing / NC)
+ *   + alpha / S * sum_s (1 / Bs) sum_ic p_s (log p_s - log m),   m = clamp(mean_s p_s, 1e-7, 1)
+ *   + lam * KL_mean(log_softmax(out_k) || log_softmax(mean_j out_j).detach())  and, with avg, the self-distillation term: both over
+ *     all B rows, as in ga_loss_fwd_bwd / ga_map_loss_fwd_bwd.
+ * Gradient of the JSD term, A = alpha / B:  g_sc = A [ (log p_sc - log m_c) + (mean_s p_sc outside [1e-7, 1] ? 1 : 0) ],
+ *     d / dx_sc = p_sc (g_sc - sum_c' p_sc' g_sc'): the clamp passes no gradient outside its range, and passes it at equality.
+ * Same conventions as ga_loss_dense_fwd_bwd: org / avg fp32 [K][B][NC]; avg, dorg, davg may be NULL; the loss is ADDED to *loss
+ * (the caller zeroes it) and not scaled; dorg / davg in `dtype` = gradient * grad_scale, every element written once, by one
+ * rounding of an fp32 value; no atomics but the one addition per workgroup onto *loss.
+ * Deviation from autograd: log p is formed as x - logsumexp(x), never as log(p), so where a probability underflows to 0 the term
+ * and its gradient are their limit 0 and the rest of the row stays finite (torch's xlogy derivative gives NaN = 0 / 0 there).
+ * One workgroup per base sample holds the log-softmax of the head-mean row of each of its S rows in LDS: 4 (S NC + 8) bytes, at
+ * most 160 KiB (S NC <= 40952).  GA_ERR_BAD_ARG, nothing launched: num_splits < 2 or > 8, B % num_splits != 0, K / B / NC < 1, a
+ * NULL org / target / loss, davg without avg, or the LDS bound. */
+int ga_loss_jsd_fwd_bwd(const float* org, const float* avg, const int64_t* target, float* loss, void* dorg, void* davg, int K, int B,
+                        int NC, int num_splits, float lam, float smoothing, float alpha, float grad_scale, int dtype,
+                        ga_stream_t stream);
 /* timm.data.Mixup (mode 'batch') on the device, lam / box drawn by the host as timm does (GA/train.py:544-557,727-728):
  *   ga_mixup_batch:  fp32 NCHW x -> out (out of place): mixup out[b] = x[b]*lam + x[B-1-b]*(1-lam), or cutmix (x[B-1-b] inside
  *                    the box [yl,yh) x [xl,xh));

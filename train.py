@@ -13,6 +13,8 @@ oracle timed by bench.py).
       rebuilt, cropped, resized and augmented on the device
   python train.py /data/imagenet ... --aug-repeats 3 -tb 1024 --cooldown-epochs 10    timm's repeated-augmentation order, each distinct
       file of a batch decoded once; --print-config prints what the flags resolve to and exits before a model is created
+  python train.py /data/imagenet ... -b 64 --aug-splits 3 --jsd-loss --aa rand-m9-mstd0.5-inc1 --reprob 0.25 --resplit    every image
+      cropped once and run as a clean and two RandAugment splits (192 rows per step), timm's JsdCrossEntropy per head
   python train.py /data/imagenet ... --output out --recovery-interval 500      out/last.pth.tar, checkpoint-N, model_best, and a recovery
       file every 500 optimizer steps, written behind the step
   python train.py /data/imagenet ... --output out --resume out/last.pth.tar    continue exactly: weights, optimizer, EMA, every random
@@ -87,8 +89,17 @@ parser.add_argument('--mixup-off-epoch', type=int, default=0)
 parser.add_argument('--reprob', type=float, default=0., metavar='PCT', help='Random erase prob (default: 0.)')
 parser.add_argument('--remode', type=str, default='pixel', help='Random erase mode (default: "pixel")')
 parser.add_argument('--recount', type=int, default=1, help='Random erase count (default: 1)')
-parser.add_argument('--resplit', action='store_true', default=False, help='Do not random erase first (clean) augmentation split '
-                    '(inert here: the reference splits only under --aug-splits, which is not built)')
+parser.add_argument('--resplit', action='store_true', default=False, help='Do not random erase first (clean) augmentation split: '
+                    'with --aug-splits N the eraser gets num_splits = N and leaves split 0 alone (inert without --aug-splits, where '
+                    'the batch has no splits)')
+# augmentation splits + the JSD consistency loss (GA/train.py:195-196,559-561,613-615: AugMixDataset + JsdCrossEntropy)
+parser.add_argument('--aug-splits', type=int, default=0, metavar='N', help='Number of augmentation splits (default: 0, valid: 0 or >=2): '
+                    '-b counts base samples, each is cropped once and run N times -- split 0 as cropped, the others through --aa with '
+                    'draws of their own -- so the model runs on N x b rows.  Excludes mixup / cutmix: their DEFAULTS (on) are switched '
+                    'off by this flag, explicit --mixup / --cutmix > 0 end the run')
+parser.add_argument('--jsd-loss', action='store_true', default=False, help='Enable Jensen-Shannon Divergence + CE loss (timm '
+                    'JsdCrossEntropy, alpha 12, per head); needs --aug-splits; takes precedence over --bce-loss')
+parser.add_argument('--split-bn', action='store_true', help='refused: separate BatchNorm layers per augmentation split are not built')
 # RandAugment on the device (MAP/train.py --aa; every recipe of MAP/train_with_script.py runs rand-mN-mstd0.5-inc1)
 parser.add_argument('--aa', type=str, default=None, metavar='NAME', help='Use AutoAugment policy, timm\'s "rand-m9-mstd0.5-inc1" form '
                     '(RandAugment only; applied on the device to the uint8 batch, ahead of every other input stage). (default: None)')
@@ -305,6 +316,31 @@ def create_scheduler(args, opt):
     return None
 
 
+def _flag_given(argv, *flags):
+    return any(a.split('=', 1)[0] in flags for a in argv)
+
+
+def resolve_aug_splits(args, argv=None):
+    """--aug-splits / --jsd-loss / --split-bn as GA/train.py:533-561,613-615 checks them.  The reference asserts that mixup is off
+    under aug splits; here mixup and cutmix default to ON, so the defaults yield to --aug-splits and only explicit ones end the run"""
+    argv = sys.argv[1:] if argv is None else argv
+    if args.split_bn:
+        raise SystemExit('train.py: --split-bn (separate BatchNorm layers per augmentation split) is not built')
+    if args.aug_splits == 1 or args.aug_splits < 0:
+        raise SystemExit(f'train.py: --aug-splits {args.aug_splits}: a split count of 1 makes no sense (0, or at least 2)')
+    if args.aug_splits > 8:
+        raise SystemExit(f'train.py: --aug-splits {args.aug_splits}: at most 8 splits are built')
+    if args.jsd_loss and args.aug_splits < 2:
+        raise SystemExit('train.py: --jsd-loss is only valid with --aug-splits >= 2 (it compares the augmentation splits)')
+    if args.aug_splits:
+        if _flag_given(argv, '--mixup', '--cutmix', '--cutmix-minmax', '--collate-mixup') and (
+                args.mixup > 0 or args.cutmix > 0. or args.cutmix_minmax is not None or args.collate_mixup):
+            raise SystemExit(f'train.py: --aug-splits {args.aug_splits} cannot be combined with mixup / cutmix (--mixup {args.mixup} '
+                             f'--cutmix {args.cutmix}): the split-major batch has no mixing partner order and the JSD loss needs '
+                             'class indices; pass --mixup 0 --cutmix 0 or leave them out')
+        args.mixup, args.cutmix = 0.0, 0.0
+
+
 def resolve_config(args, world, rank, train_loader=None):
     """the settings the flags resolve to, checked on the host before the model is created (what --print-config prints).  Sets
     args.grad_accumulation from -tb and args.crop_pct to its default."""
@@ -318,6 +354,7 @@ def resolve_config(args, world, rank, train_loader=None):
                              'rank(s)): no whole number of batches per optimizer step')
     if args.crop_pct is None:
         args.crop_pct = 0.875                  # timm's evaluation default
+    resolve_aug_splits(args)
     try:
         optimizer = A.optimizer_config(args.opt, momentum=args.momentum, eps=args.opt_eps, betas=args.opt_betas)
     except ValueError as e:
@@ -328,7 +365,9 @@ def resolve_config(args, world, rank, train_loader=None):
                        ('grad_accumulation', args.grad_accumulation), ('epochs', args.epochs + args.cooldown_epochs),
                        ('cooldown_epochs', args.cooldown_epochs), ('aug_repeats', args.aug_repeats),
                        ('selected_round', args.selected_round), ('crop_pct', args.crop_pct), ('interpolation', args.interpolation),
-                       ('drop', args.drop), ('opt', args.opt.lower()), ('optimizer', optimizer), ('schedule', schedule_config(args))])
+                       ('drop', args.drop), ('opt', args.opt.lower()), ('optimizer', optimizer), ('schedule', schedule_config(args)),
+                       ('aug_splits', args.aug_splits), ('jsd_loss', bool(args.jsd_loss)),
+                       ('model_batch', args.batch_size * max(1, args.aug_splits))])
     if train_loader is not None:
         cfg.update(train_images=len(train_loader.dataset), batches_per_epoch=len(train_loader),
                    distinct_files_per_epoch=train_loader.distinct_files(0))
@@ -489,10 +528,17 @@ def main():
         raise SystemExit('train.py: --collate-mixup needs --mixup > 0, --cutmix > 0 or --cutmix-minmax')
     # RandomErasing as timm's create_loader builds it (re_prob / re_mode / re_count: the MAX count; num_splits 0 without aug-splits)
     random_erasing = None
+    # --aug-splits N: the eraser keeps the clean split only with --resplit (timm create_loader: re_num_splits)
+    aug_splits = A.AugSplits(args.aug_splits) if args.aug_splits else None
     if args.reprob > 0.:
-        random_erasing = A.RandomErasing(probability=args.reprob, mode=args.remode, max_count=args.recount, num_splits=0,
-                                         seed=args.seed + rank)
-    step_fn = A.TrainStep(model, opt, args.batch_size, lam=lam, loss='bce' if args.bce_loss else 'ce',
+        random_erasing = A.RandomErasing(probability=args.reprob, mode=args.remode, max_count=args.recount,
+                                         num_splits=args.aug_splits if (args.resplit and args.aug_splits) else 0, seed=args.seed + rank)
+    if aug_splits is not None and rank == 0:
+        _logger.info('--aug-splits %d: %d base samples per batch, the model runs on %d rows; mixup / cutmix are off; loss: %s',
+                     args.aug_splits, args.batch_size, args.batch_size * args.aug_splits,
+                     'JSD (alpha 12) + CE on the clean split' if args.jsd_loss else 'the ordinary loss over all rows')
+    step_fn = A.TrainStep(model, opt, args.batch_size * max(1, args.aug_splits), lam=lam,
+                          loss='jsd' if args.jsd_loss else 'bce' if args.bce_loss else 'ce', aug_splits=aug_splits,
                           smoothing=args.smoothing, grad_accumulation=args.grad_accumulation,
                           clip_grad=args.clip_grad, clip_mode=args.clip_mode, broadcast_buffers=not args.no_ddp_bb,
                           mixup_fn=mixup_fn, bce_target_thresh=args.bce_target_thresh, comm=comm, random_erasing=random_erasing,
